@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the MI355X pairwise-registration hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload scene|precomputed]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload scene|precomputed] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, the step spread
+and the configuration).  --dump-outputs DIR also writes what the last timed step returned (DIR/records.npy).
+--full adds everything else the line can report: the per-class profile and the roofline object, the secondary
+timed leg at the other maths, the accuracy on the full-size goldens and the CPU baselines.
 
 One process per GPU (torchrun for N>1, RCCL over xGMI).  A *step* is one pass
 of the hot path over one batch of synthetic input resident in HBM:
@@ -15,7 +20,7 @@ of the hot path over one batch of synthetic input resident in HBM:
                Procrustes -> all-gather.
 
 Weak scaling: every rank processes its own scene / pair batch (different seed).
-Rank 0 prints ONE JSON line (the driver contract); the roofline object prices
+Rank 0 prints ONE JSON line (the driver contract).  With --full the roofline object prices
 the dominant kernel class from per-launch hipEvent timings taken inside the
 timed region (plus the SURVEY §8d whole-step floor); cpu_baseline times the
 reference's CPU op sequence (oracle/torch_port.py, numpy FCGF restatement) on a
@@ -488,7 +493,8 @@ def class_peak_tflops(cls, knobs):
 
 
 def timed_run(wl, args, world, pipelined, barrier):
-    """warmup, one untimed profiled step (per-class breakdown, dominant class), the timed steps"""
+    """warmup, with --full one untimed profiled step (per-class breakdown, dominant class), the timed steps
+    (a plain run records no per-launch events and reads no profile: prof, prof_all and dom are None)"""
     from lib import _native
 
     def run_step():
@@ -503,18 +509,19 @@ def timed_run(wl, args, world, pipelined, barrier):
         # the timed region then records events only around the dominant class's launches (events on
         # every launch cost ~1 ms per step).  --prof-seq (PMC attribution of exactly the timed steps'
         # launches) records every class in the timed region instead.
-        prof_all, dom = None, None
+        prof, prof_all, dom = None, None, None
         torch.cuda.synchronize()
-        _native.prof_mask(None)
-        if not args.prof_seq:
-            _native.prof_set(1)
-            wl.gather(wl.step(), world)   # stages back to back: per-class times without overlap
-            torch.cuda.synchronize()
-            prof_all = {k: _native.prof_get(k) for k in _native.PROF_KINDS}
-            _native.prof_set(0)
-            dom = max(prof_all, key=lambda k: prof_all[k][0])
-            _native.prof_mask([dom])
-        _native.prof_set(0 if args.no_prof else 1)
+        if args.full:
+            _native.prof_mask(None)
+            if not args.prof_seq:
+                _native.prof_set(1)
+                wl.gather(wl.step(), world)   # stages back to back: per-class times without overlap
+                torch.cuda.synchronize()
+                prof_all = {k: _native.prof_get(k) for k in _native.PROF_KINDS}
+                _native.prof_set(0)
+                dom = max(prof_all, key=lambda k: prof_all[k][0])
+                _native.prof_mask([dom])
+            _native.prof_set(0 if args.no_prof else 1)
         barrier()
         torch.cuda.synchronize()
         # per-step boundaries for the median: an event on every stream a step enqueues on, recorded after the
@@ -538,15 +545,16 @@ def timed_run(wl, args, world, pipelined, barrier):
         dt = t1 - t0
         ends = [max(ev0.elapsed_time(e) for e in evs) for evs in step_ev]
         step_ms = np.diff([0.0] + ends)
-        prof = {k: _native.prof_get(k) for k in _native.PROF_KINDS}
-        if prof_all is None:
-            prof_all = {k: tuple(x / max(args.steps, 1) for x in v) for k, v in prof.items()}
-            dom = max(prof, key=lambda k: prof[k][0])
-        if args.prof_seq and int(os.environ.get("RANK", "0")) == 0:
-            with open(args.prof_seq, "w") as f:
-                json.dump(_native.prof_seq(), f)
-        _native.prof_set(0)
-        _native.prof_mask(None)
+        if args.full:
+            prof = {k: _native.prof_get(k) for k in _native.PROF_KINDS}
+            if prof_all is None:
+                prof_all = {k: tuple(x / max(args.steps, 1) for x in v) for k, v in prof.items()}
+                dom = max(prof, key=lambda k: prof[k][0])
+            if args.prof_seq and int(os.environ.get("RANK", "0")) == 0:
+                with open(args.prof_seq, "w") as f:
+                    json.dump(_native.prof_seq(), f)
+            _native.prof_set(0)
+            _native.prof_mask(None)
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():   # max over ranks
         from lib import distributed as D
@@ -614,7 +622,7 @@ def golden_accuracy(dev):
     return r
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -647,8 +655,19 @@ def main():
                          "all-gathers and the guard all-reduce replaced by local copies of the same sizes) -- the "
                          "per-rank step of the N-GPU strong-scaling split, whose aggregate rate the line reports")
     ap.add_argument("--prof-seq", default=None, help="write the per-launch kernel-class sequence of the timed "
-                    "steps (JSON) for PMC attribution (tools/pmc_traffic.py)")
-    args = ap.parse_args()
+                    "steps (JSON) for PMC attribution (tools/pmc_traffic.py); needs --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them returned as DIR/records.npy (float32: the "
+                    "gathered per-pair records, 9 of R, 3 of t, the inlier fraction); the inputs are seeded, so two "
+                    "builds run with the same arguments can be compared record for record")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what the headline does not need: the per-class profile and the "
+                    "roofline (per-launch events in the timed region), the secondary leg at the other maths, the "
+                    "accuracy on the full-size goldens, the CPU baselines (--no-prof, --no-secondary and "
+                    "--no-cpu-baseline drop single parts of it)")
+    args = ap.parse_args(argv)
+    if args.prof_seq and not args.full:
+        ap.error("--prof-seq records the per-launch profile of the timed steps: run it with --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -708,6 +727,49 @@ def main():
     pairs_per_step = int(rec.shape[0]) if pair_sharded else int(rec.shape[-2]) * world
     value = pairs_per_step * args.steps / dt
     ms_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "records.npy"), rec.detach().float().cpu().numpy())
+
+    def finish(roof=None, cpu=None, accuracy=None, secondary=None):
+        line = {"metric": METRIC if args.workload == "scene" else METRIC + " [filter+SVD only: precomputed corr.]",
+                "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+                "ms_per_step_median": round(float(np.median(step_ms)), 3),
+                "ms_per_step_min_max": [round(float(step_ms.min()), 3), round(float(step_ms.max()), 3)],
+                "higher_is_better": True,
+                "scaling": "strong" if pair_sharded else "weak", "vs_baseline": None, "dtype": math_info["dtype"],
+                "data": "synthetic",
+                "config": dict(wl.config(), math=args.math,
+                               oanet_point_layout={1: "chunk-major", 0: "row-major"}.get(
+                                   _native.lib().mvr_oan_last_layout(), "none"),
+                               emulated=("rank 0 of %d on ONE GPU: collectives replaced by local copies of the same "
+                                         "sizes; value = the whole job's pairs / rank 0's step" % world)
+                               if emulate else None,
+                               spconv_presplit_planes=bool(_fcgf_mod().PRESPLIT), spatial_map_order=bool(
+                                   _sparse_mod().SPATIAL_MAPS), library=_native.source_hash(),
+                               parallelism=(("pairs%d (one scene per step: fragments and pair batch sharded over %d "
+                                             "ranks, %s all-gather of samples and records)"
+                                             if args.workload == "scene" else
+                                             "pairs%d (one evaluation per step: its 32-pair loader batches in "
+                                             "contiguous blocks over %d ranks, %s all-gather of the records)")
+                                            % (world, world, "RCCL" if backend == "nccl" else backend)
+                                            if pair_sharded else
+                                            "dp%d (one scene per rank, %s all-gather of records)"
+                                            % (world, "RCCL" if backend == "nccl" else backend)),
+                               schedule=("3-stream pipeline over consecutive scenes: voxelisation + coordinate levels "
+                                         "of scene k+1, FCGF + feature NN of scene k, OANet + Procrustes of scene "
+                                         "k-1; every timed step runs every stage in full"
+                                         if pipelined else "stages back to back on one stream")),
+                "roofline": roof, "cpu_baseline": cpu, "accuracy": accuracy, "secondary": secondary}
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if use_pg:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+    if not args.full:   # the headline alone: nothing below is needed for it
+        return finish()
 
     # FCGF sparse convs: the launch-level ProfScope cannot see how many kernel-map pairs a launch has (no host
     # sync); the class's algorithmic FLOPs / bytes are counted here from the scene's kernel maps instead
@@ -819,39 +881,7 @@ def main():
         if args.workload == "scene":   # the instruction set of the C sparse conv on this host (oracle/csrc clone)
             from oracle.fcgf import isa
             cpu["fcgf_isa"] = isa()
-    line = {"metric": METRIC if args.workload == "scene" else METRIC + " [filter+SVD only: precomputed corr.]",
-            "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
-            "ms_per_step_median": round(float(np.median(step_ms)), 3),
-            "ms_per_step_min_max": [round(float(step_ms.min()), 3), round(float(step_ms.max()), 3)],
-            "higher_is_better": True,
-            "scaling": "strong" if pair_sharded else "weak", "vs_baseline": None, "dtype": math_info["dtype"], "data": "synthetic",
-            "config": dict(wl.config(), math=args.math,
-                           oanet_point_layout={1: "chunk-major", 0: "row-major"}.get(
-                               _native.lib().mvr_oan_last_layout(), "none"),
-                           emulated=("rank 0 of %d on ONE GPU: collectives replaced by local copies of the same "
-                                     "sizes; value = the whole job's pairs / rank 0's step" % world) if emulate else None,
-                           spconv_presplit_planes=bool(_fcgf_mod().PRESPLIT), spatial_map_order=bool(
-                               _sparse_mod().SPATIAL_MAPS), library=_native.source_hash(),
-                           parallelism=(("pairs%d (one scene per step: fragments and pair batch sharded over %d "
-                                         "ranks, %s all-gather of samples and records)"
-                                         if args.workload == "scene" else
-                                         "pairs%d (one evaluation per step: its 32-pair loader batches in contiguous "
-                                         "blocks over %d ranks, %s all-gather of the records)")
-                                        % (world, world, "RCCL" if backend == "nccl" else backend)
-                                        if pair_sharded else
-                                        "dp%d (one scene per rank, %s all-gather of records)"
-                                        % (world, "RCCL" if backend == "nccl" else backend)),
-                           schedule=("3-stream pipeline over consecutive scenes: voxelisation + coordinate levels of "
-                                     "scene k+1, FCGF + feature NN of scene k, OANet + Procrustes of scene k-1; every "
-                                     "timed step runs every stage in full"
-                                     if pipelined else "stages back to back on one stream")),
-            "roofline": roof, "cpu_baseline": cpu, "accuracy": accuracy, "secondary": secondary}
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if use_pg:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    finish(roof, cpu, accuracy, secondary)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
-"""Summarise bench.py JSON lines from logs: step time, median, and the per-class ms (profiled sequential step).
-usage: python tools/ab_table.py gpurun_out/bench*.log"""
+"""Summarise bench.py JSON lines from logs: step time, median, and the per-class ms (the profiled sequential step
+of a `bench.py --full` run; zeros for a plain run, which has no profile).
+usage: python tools/ab_table.py <logs of bench.py runs>"""
 import json
 import sys
 
@@ -13,6 +14,6 @@ for fn in sys.argv[1:]:
     if line is None:
         print("%-28s (no result)" % fn)
         continue
-    c = line.get("roofline", {}).get("classes", {})
+    c = (line.get("roofline") or {}).get("classes", {})
     print("%-28s %8.3f %8.3f %8.0f  %s" % (fn.split("/")[-1][:28], line["ms_per_step"], line.get("ms_per_step_median", 0),
                                         line["value"], "  ".join("%11.3f" % c.get(k, [0])[0] for k in cls_order)))

@@ -14,7 +14,7 @@ echo smoke ok
 bash tools/pmc_bench.sh $O/pmc > $O/pmc.log 2>&1 || { tail -20 $O/pmc.log; exit 1; }
 python3 tools/pmc_traffic.py $O/pmc --out $O/pmc_traffic.json > $O/pmc_traffic.log 2>&1 || { tail -20 $O/pmc_traffic.log; exit 1; }
 cp $O/pmc_traffic.json profiles/pmc_traffic.json
-timeout -k 10 400 python -u bench.py > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.log 2>&1 || { tail -30 $O/bench.log; exit 1; }
 tail -c 600 $O/bench.log
 bash tools/prof_bench.sh $O/prof_pipe --no-secondary > $O/prof_pipe.log 2>&1 || { tail -20 $O/prof_pipe.log; exit 1; }
 bash tools/prof_bench.sh $O/prof_seq --no-pipeline --no-secondary --steps 7 --warmup 2 > $O/prof_seq.log 2>&1 || { tail -20 $O/prof_seq.log; exit 1; }

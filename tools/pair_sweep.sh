@@ -11,6 +11,6 @@ PAIRS=("$@")
 for p in "${PAIRS[@]}"; do
   steps=$(( 4000 / p )); [ $steps -lt 5 ] && steps=5
   timeout -k 10 240 python3 "$R/bench.py" --workload precomputed --pairs $p --steps $steps --warmup 3 \
-    --no-cpu-baseline > "$OUT/pairs_$p.json" 2> "$OUT/pairs_$p.err" || exit $?
+    --full --no-cpu-baseline > "$OUT/pairs_$p.json" 2> "$OUT/pairs_$p.err" || exit $?
   echo "pairs $p done"
 done

@@ -10,6 +10,6 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   MVR_PROF_MARK=1 timeout -k 10 600 rocprofv3 --pmc $c -d "$OUT/$c" -o pmc --output-format csv -- \
-    python3 "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-pipeline --prof-seq "$OUT/seq_$c.json" "${@:2}" \
+    python3 "$R/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --no-pipeline --prof-seq "$OUT/seq_$c.json" "${@:2}" \
     > "$OUT/bench_$c.log" 2>&1 || exit $?
 done

@@ -92,7 +92,7 @@ def main():
                   "pmc_bytes_per_launch": fb + wb, "algorithmic_bytes_per_launch": ab,
                   "pmc_over_algorithmic": (fb + wb) / ab if ab else None,
                   "kernels": dict(sorted(names[c].items()))}
-    doc = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --steps 1 --warmup 1` with "
+    doc = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --full --steps 1 --warmup 1` with "
                      "MVR_PROF_MARK=1 (tools/pmc_bench.sh): dispatches joined to the timed step's launch sequence "
                      "by region markers; FETCH x2 (gfx950 16 B/lane correction), KB -> B",
            "math": a.math, "lib_hash": lib_hash(), "classes": res}

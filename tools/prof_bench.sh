@@ -6,4 +6,4 @@ OUT="$R/$1"; shift
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT" -o trace --output-format csv -- \
-  python3 "$R/bench.py" --no-cpu-baseline "$@"
+  python3 "$R/bench.py" --full --no-cpu-baseline "$@"
