@@ -1,0 +1,73 @@
+"""Multiview synchronisation of a scene's pairwise trajectory: traj.txt -> poses.txt + traj_sync.txt.
+
+Reads the `traj.txt` the pairwise benchmark writes for a scene (scripts/benchmark_pairwise_registration.py: per
+written pair the metadata `i j True` and, in the 3DMatch log convention, T_log = inv(T) of the estimate x_j ~ T x_i),
+synchronises the pairs on the GPU (lib.multiview.synchronize) and writes into --out
+  poses.txt      one block per fragment: metadata `i i N` and the 4 x 4 pose M_i (fragment i -> the anchor's frame),
+  traj_sync.txt  the same pairs and flags with inv(M_j^-1 M_i): the synchronised pairwise estimates in the log
+                 convention, readable by the benchmark's report code like any traj.txt.
+
+usage: python -m scripts.multiview_sync --traj results/RegBlock/all/<scene>/traj.txt --n_fragments 60 --out DIR
+           [--anchor 0] [--irls 5] [--c_rot 0.1] [--c_trans 0.1]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+from lib.utils import ensure_dir, read_trajectory, write_trajectory  # noqa: E402
+from lib.multiview import synchronize, pairwise_from_poses  # noqa: E402
+
+
+def sync_trajectory(keys, traj, n_fragments, anchor=0, irls=0, c_rot=0.1, c_trans=0.1):
+    """keys [E,3] (i, j, flag) and traj [E,4,4] as read_trajectory returns them (T_log = inv(T)) ->
+    (poses [N,4,4], traj_sync [E,4,4] in the log convention, the dict synchronize returned)."""
+    traj = np.asarray(traj, np.float64).reshape(-1, 4, 4)
+    pairs = np.asarray([[int(k[0]), int(k[1])] for k in keys], np.int64).reshape(-1, 2)
+    T = np.linalg.inv(traj) if len(traj) else traj
+    res = synchronize(T[:, :3, :3], T[:, :3, 3], pairs, int(n_fragments), anchor=anchor, irls_iters=irls,
+                      c_rot=c_rot, c_trans=c_trans)
+    R, t = np.asarray(res["R"], np.float64), np.asarray(res["t"], np.float64)
+    poses = np.tile(np.eye(4), (int(n_fragments), 1, 1))
+    poses[:, :3, :3], poses[:, :3, 3] = R, t
+    T_sync = np.asarray(pairwise_from_poses(R, t, pairs), np.float64)
+    return poses, (np.linalg.inv(T_sync) if len(T_sync) else T_sync), res
+
+
+def write_poses(poses, filename):
+    """one block per fragment in the trajectory files' layout: `i i N`, then the 4 rows of M_i"""
+    n = poses.shape[0]
+    with open(filename, "w") as f:
+        for i in range(n):
+            f.write("%d\t%d\t%d\n" % (i, i, n))
+            f.write("\n".join("\t".join("{0:.12f}".format(v) for v in row) for row in poses[i].tolist()))
+            f.write("\n")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--traj", required=True, help="a scene's traj.txt written by the pairwise benchmark")
+    ap.add_argument("--n_fragments", type=int, required=True)
+    ap.add_argument("--anchor", type=int, default=0)
+    ap.add_argument("--irls", type=int, default=5, help="IRLS re-weighting passes (0: the plain closed form)")
+    ap.add_argument("--c_rot", type=float, default=0.1)
+    ap.add_argument("--c_trans", type=float, default=0.1)
+    ap.add_argument("--out", required=True, help="output directory")
+    a = ap.parse_args(argv)
+    keys, traj = read_trajectory(a.traj)
+    poses, traj_sync, res = sync_trajectory(keys, traj, a.n_fragments, a.anchor, a.irls, a.c_rot, a.c_trans)
+    ensure_dir(a.out)
+    write_poses(poses, os.path.join(a.out, "poses.txt"))
+    write_trajectory(traj_sync, [list(k) for k in keys], os.path.join(a.out, "traj_sync.txt"))
+    member = np.asarray(res["member"])
+    print("synchronised %d pairs over %d fragments (%d connected to anchor %d, status %d) -> %s"
+          % (len(keys), a.n_fragments, int(member.sum()), a.anchor, int(np.asarray(res["status"])), a.out))
+
+
+if __name__ == "__main__":
+    main()

@@ -83,6 +83,38 @@ int mvr_ransac(const double* x1, const double* x2, int64_t x_pstride, const int3
                int32_t* best_iter, double* hyp_out, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Multiview pose synchronisation, batched over scenes (csrc/sync.hip).
+ * The closed-form weighted solve of the paper's sections 3.2-3.3 with optional IRLS; the reference never released
+ * this stage (its README.md:116), so it replaces nothing: it turns the pairwise estimates of a scene into one pose
+ * per fragment.
+ *   Edge e of scene s is row s*e_sstride + e of R_pair [.,9] (row-major), t_pair [.,3], ij [.,2], w [.] (NULL: all
+ *   ones): x_j ~ R x_i + t with source i = ij[.,0], target j = ij[.,1] (lib.utils.pair_index order), w >= 0; any
+ *   i != j in either order, repeated edges allowed.  n_edges [S], n_frags [S] are device arrays
+ *   (<= max_edges, <= max_frags).  Fragment f of scene s is row s*f_sstride + f of R [.,9], t [.,3], member [.].
+ *   Poses: X = R_f x_f + t_f in the frame of fragment `anchor` (R = I, t = 0 there).  member[f] = 1 for the
+ *   fragments connected to the anchor over edges with w > 0; the others come out as R = I, t = 0, member = 0 and
+ *   their edges with weight 0.  irls_iters re-weighting passes w <- w0 / (1 + (e/c_rot)^2) / (1 + (d/c_trans)^2)
+ *   with e = |R_k - R_j^T R_i|_F and d = |t_i - t_j - R_j t_k|_2; w_out, res_rot, res_trans [., same rows as w]
+ *   are the last pass's weights and residuals.  member, w_out, res_rot, res_trans may be NULL.
+ *   status [S], bits: 1 some fragment is not a member; 2 the eigen-solve of some pass stopped at its iteration
+ *   cap; 4 an edge was ignored (index out of range, i == j, a non-finite value or a negative weight; it comes out
+ *   with weight and residuals 0), or the scene is invalid (anchor >= n_frags[s], a count negative or above its
+ *   maximum): the whole scene comes out as identity, member = 0.
+ *   fp64 throughout; one workgroup per scene, every pass inside the one launch.  max_frags <= MVR_SYNC_MAX_FRAGS;
+ *   workspace (8-byte aligned) >= mvr_sync_workspace_bytes(S, max_frags, max_edges).  MVR_EINVAL for negative
+ *   S / max_frags / max_edges / irls_iters, max_frags above the maximum, anchor outside [0, max_frags) (when
+ *   max_frags > 0), c_rot or c_trans <= 0 with irls_iters > 0, a short workspace, and with S > 0 a NULL n_edges,
+ *   n_frags, status, R or t (max_frags > 0) or R_pair, t_pair or ij (max_edges > 0).
+ * ---------------------------------------------------------------------- */
+#define MVR_SYNC_MAX_FRAGS 128
+size_t mvr_sync_workspace_bytes(int S, int max_frags, int max_edges);
+int mvr_sync_poses(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w, int64_t e_sstride,
+                   const int32_t* n_edges, const int32_t* n_frags, int S, int max_frags, int max_edges, int anchor,
+                   int irls_iters, double c_rot, double c_trans, double* R, double* t, int64_t f_sstride,
+                   int32_t* member, double* w_out, double* res_rot, double* res_trans, int32_t* status,
+                   void* workspace, size_t workspace_bytes, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Process-wide selections (the only two; every other choice a launch makes is a function of its arguments).
  * mvr_set_math: the operand arithmetic of every kernel that has a choice.  0 (default) f32eq: every fp32 product on
  *   the three-term bf16 split (h + m + l, 6 MFMAs: fp32-equivalent operands).  1 split16: the two-term fp16 split
