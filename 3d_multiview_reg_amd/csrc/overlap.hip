@@ -13,14 +13,11 @@
 #include "common.hpp"
 #include "prof.hpp"
 #include "radix.hpp"
+#include "rindex.hpp"
 #include "mvreg.h"
 
 namespace mvr {
 namespace {
-
-constexpr uint64_t OV_EMPTY = ~0ull;
-constexpr int OV_BITS = 16;                 // bits per cell / voxel coordinate
-constexpr int64_t OV_BIAS = 1 << 15;        // signed cell coordinates are biased by 2^15
 
 __device__ __forceinline__ int frag_of(const int64_t* off, int B, int64_t i) {
   int lo = 0, hi = B;   // off[lo] <= i < off[hi]
@@ -30,20 +27,6 @@ __device__ __forceinline__ int frag_of(const int64_t* off, int B, int64_t i) {
   }
   return lo;
 }
-__device__ __forceinline__ uint64_t pack_key(int b, int64_t x, int64_t y, int64_t z) {
-  const uint64_t m = (1ull << OV_BITS) - 1;
-  return ((uint64_t)b << (3 * OV_BITS)) | (((uint64_t)x & m) << (2 * OV_BITS)) | (((uint64_t)y & m) << OV_BITS) |
-         ((uint64_t)z & m);
-}
-__device__ __forceinline__ uint64_t hash64(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
-
 // ---------------------------------------------------------------------------- voxel centroids
 __global__ void frag_min_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ off, double* minb) {
   __shared__ double red[3][256];
@@ -121,14 +104,6 @@ __global__ void fill_i64_kernel(int64_t* p, int64_t n, int64_t v) {
 }
 
 // ---------------------------------------------------------------------------- radius index
-struct RIndex {
-  int32_t* sidx;      // [M] point ids in (fragment, cell) order
-  uint64_t* skey;     // [M]
-  uint64_t* hkeys;    // [cap]
-  int2* hval;         // [cap] (start, end) of the cell in the sorted order
-  uint64_t cap;
-};
-
 __global__ void cell_key_kernel(const double* __restrict__ xyz, const int64_t* __restrict__ off, int B, int64_t M,
                                 double r, uint64_t* keys, uint64_t* keys2, int32_t* idx) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,16 +136,6 @@ __global__ void cell_insert_kernel(RIndex ix, int64_t M) {
   }
   if (first) ix.hval[h].x = (int)i;
   if (last) ix.hval[h].y = (int)i + 1;
-}
-
-__device__ __forceinline__ int2 cell_find(const RIndex& ix, uint64_t k) {
-  uint64_t h = hash64(k) & (ix.cap - 1);
-  while (true) {
-    const uint64_t s = ix.hkeys[h];
-    if (s == k) return ix.hval[h];
-    if (s == OV_EMPTY) return make_int2(0, 0);
-    h = (h + 1) & (ix.cap - 1);
-  }
 }
 
 // blockIdx.y = 2 p + d: queries of fragment pairs[p][d] mapped by T[p][d] (3x4 row-major) against the
@@ -209,31 +174,10 @@ __global__ void overlap_count_kernel(RIndex ix, const double* __restrict__ xyz, 
 
 // ---------------------------------------------------------------------------- host helpers
 inline unsigned nb(int64_t n) { return (unsigned)((n + 255) / 256); }
-inline char* take(char*& p, size_t b) {
-  p = reinterpret_cast<char*>(((uintptr_t)p + 255) & ~(uintptr_t)255);
-  char* r = p;
-  p += b;
-  return r;
-}
 size_t sort_bytes(int64_t n) { return radix_ws_bytes(n > 0 ? n : 1); }
 size_t scan_bytes(int64_t n) { return scan_ws_bytes(n > 0 ? n : 1); }
 // key bits of pack_key for fragments [0, B): 48 coordinate bits + the fragment index
 int key_bits(int B) { return 3 * OV_BITS + (B > 1 ? 32 - __builtin_clz((unsigned)(B - 1)) : 1); }
-uint64_t cap_for(int64_t M) {
-  uint64_t c = 1024;
-  while (c < (uint64_t)(2 * (M > 0 ? M : 1))) c <<= 1;
-  return c;
-}
-RIndex index_view(void* base, int64_t M) {
-  char* p = reinterpret_cast<char*>(base);
-  RIndex ix{};
-  ix.cap = cap_for(M);
-  ix.sidx = reinterpret_cast<int32_t*>(take(p, (size_t)(M > 0 ? M : 1) * 4));
-  ix.skey = reinterpret_cast<uint64_t*>(take(p, (size_t)(M > 0 ? M : 1) * 8));
-  ix.hkeys = reinterpret_cast<uint64_t*>(take(p, ix.cap * 8));
-  ix.hval = reinterpret_cast<int2*>(take(p, ix.cap * 8));
-  return ix;
-}
 size_t index_bytes(int64_t M) {
   const size_t m = (size_t)(M > 0 ? M : 1);
   return m * 12 + cap_for(M) * 16 + 5 * 256;

@@ -101,6 +101,9 @@ _SIGS = {
     "mvr_radius_index_build": (c_int, [c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_size, c_vp]),
     "mvr_radius_overlap_count": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64,
                                          ctypes.c_double, c_vp, c_vp]),
+    "mvr_icp_refine": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_int,
+                               ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp,
+                               c_vp, c_vp, c_vp]),
     "mvr_hash_table_bytes": (c_size, [c_i64]),
     "mvr_voxelize_workspace_bytes": (c_size, [c_i64]),
     "mvr_voxelize_hint_workspace_bytes": (c_size, [c_i64, c_i64]),

@@ -1,0 +1,101 @@
+"""Fine registration: batched point-to-point ICP on the fragments' own points (csrc/icp.hip mvr_icp_refine; the
+semantics are in DESIGN.md 4.19 and include/mvreg.h).
+
+The reference stops at the coarse estimate (Procrustes or RANSAC over the sampled correspondences); its users
+follow it with Open3D's `registration_icp`.  `icp_refine` does that for every pair of a scene in one launch, on the
+radius index a `FragmentOverlap` already holds; `icp_pair` keeps the one-pair shape of `registration_icp`.  Restated
+from the maths and pinned to tests/icp_oracle.py: Open3D parity is unpinned.
+
+Convention: T maps source coordinates into the target's frame, x_target ~ R x_source + t (rot_est / trans_est of
+filter_correspondences, the input of lib.multiview.synchronize) — the inverse of the `trans` of
+FragmentOverlap.ratios."""
+import numpy as np
+import torch
+
+from lib import _native as N
+
+STATUS_FEW_CORRESPONDENCES, STATUS_ITERATION_CAP, STATUS_INVALID_PAIR = 1, 2, 4
+
+
+def _check_settings(name, max_dist, max_iters, tol_fitness, tol_rmse):
+    if not max_dist > 0.0:
+        raise ValueError("%s: max_dist must be positive" % name)
+    if int(max_iters) < 0:
+        raise ValueError("%s: max_iters must not be negative" % name)
+    if not (tol_fitness >= 0.0 and tol_rmse >= 0.0):
+        raise ValueError("%s: the tolerances must not be negative" % name)
+
+
+def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, return_trace=False):
+    """Refine the transform of every pair on the points of `fo` (a lib.overlap.FragmentOverlap: its centroids for
+    method 'FCGF', its raw points for '3DMatch').
+
+    pairs [P,2] (source, target) fragment indices; T_init [P,4,4] or [P,3,4], numpy or torch, any float dtype;
+    max_dist: the correspondence distance, at most fo.r (None: fo.r).  Stops after max_iters solves, or when fitness
+    and rmse both change by less than their tolerances (absolute); both tolerances 0 run exactly max_iters.
+    Returns a dict of fp64 T [P,4,4], fp64 fitness / rmse [P], int32 n_corr / iters / status [P] (STATUS_* bits) and,
+    with return_trace, fp64 trace [P, max_iters + 1, 2]: (fitness, rmse) of every evaluation, -1 after the last.
+    The outputs stay on the device when T_init was on the device; otherwise they come back on the host (numpy for
+    numpy inputs)."""
+    max_dist = float(fo.r if max_dist is None else max_dist)
+    _check_settings("icp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
+    if max_dist > fo.r:
+        raise ValueError("icp_refine: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
+                         "radius >= max_dist)" % (max_dist, fo.r))
+    was_numpy = not torch.is_tensor(T_init)
+    Tin = torch.as_tensor(T_init)
+    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("icp_refine: T_init must be a float [P,4,4] or [P,3,4]")
+    ij = torch.as_tensor(pairs)
+    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
+        raise ValueError("icp_refine: pairs must be [P,2] with one row per transform")
+    N.require_hip()
+    on_dev = Tin.device.type == "cuda"
+    dev = fo.device
+    P, rows = int(Tin.shape[0]), int(max_iters) + 1
+    T0 = Tin[:, :3, :].to(dev, torch.float64).contiguous()
+    ij = ij.to(dev, torch.int64).contiguous()
+    T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
+    fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
+    n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    trace = torch.empty(P, rows, 2, dtype=torch.float64, device=dev) if return_trace else None
+    N.check(N.lib().mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M,
+                                   fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, int(max_iters), float(tol_fitness),
+                                   float(tol_rmse), N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr),
+                                   N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream()), "mvr_icp_refine")
+    T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
+    T4[:, :3], T4[:, 3, 3] = T, 1.0
+    out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
+    if return_trace:
+        out["trace"] = trace
+    if not on_dev:
+        out = {k: v.cpu() for k, v in out.items()}
+        if was_numpy:
+            out = {k: v.numpy() for k, v in out.items()}
+    return out
+
+
+def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, **kw):
+    """One pair in the shape of Open3D's registration_icp(source, target, max_correspondence_distance, init):
+    src_xyz [n,3], tgt_xyz [m,3], T_init [4,4] or [3,4] with x_target ~ T x_source.  voxel_size None: the raw points;
+    a value: Open3D-style voxel centroids of both clouds (lib.overlap).  **kw: max_iters, tol_fitness, tol_rmse,
+    return_trace of icp_refine.  Returns icp_refine's dict without the leading [P]."""
+    from lib.overlap import FragmentOverlap
+    _check_settings("icp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
+                    kw.get("tol_rmse", 0.0))
+    if voxel_size is not None and not voxel_size > 0.0:
+        raise ValueError("icp_pair: voxel_size must be positive")
+    for name, x in (("src_xyz", src_xyz), ("tgt_xyz", tgt_xyz)):
+        shape = tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("icp_pair: %s must be [n,3]" % name)
+    Tin = torch.as_tensor(T_init)
+    if tuple(Tin.shape) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("icp_pair: T_init must be a float [4,4] or [3,4]")
+    if voxel_size is None:
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=max_dist)
+    else:
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=max_dist)
+    T0 = T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None]
+    out = icp_refine(fo, [[0, 1]], T0, max_dist, **kw)
+    return {k: v[0] for k, v in out.items()}

@@ -28,12 +28,15 @@ def _radius(method, voxel_size):
 
 class FragmentOverlap(object):
     """Downsampled (method 'FCGF') or raw ('3DMatch') fragments of a scene with a radius index on the
-    GPU.  xyz_list: list of [n_b, 3] arrays / tensors (any float dtype)."""
+    GPU.  xyz_list: list of [n_b, 3] arrays / tensors (any float dtype).  radius: the index's cell size and the
+    match radius instead of the method's (lib.icp refines on an index whose cells cover its search ball)."""
 
-    def __init__(self, xyz_list, method="FCGF", voxel_size=0.025, device=None):
+    def __init__(self, xyz_list, method="FCGF", voxel_size=0.025, device=None, radius=None):
         N.require_hip()
         dev = device or torch.device("cuda", torch.cuda.current_device())
         self.method, self.voxel_size, self.r = method, float(voxel_size), _radius(method, voxel_size)
+        if radius is not None:
+            self.r = float(radius)
         L = N.lib()
         B = len(xyz_list)
         pts = [torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x) for x in xyz_list]

@@ -10,7 +10,9 @@ report), with the per-pair host loop replaced by batched GPU calls:
     (Redwood) on the GPU (lib/overlap.py; every pair of a loader batch in one FragmentOverlap.ratios call),
     trajectories written per scene (benchmark:222-245, with the
     bool-flag fix of lib/utils.py write_trajectory), then precision / recall / rotation and translation
-    errors per scene against gt.log / gt.info (benchmark:250-345).
+    errors per scene against gt.log / gt.info (benchmark:250-345);
+  * `--icp` (not in the reference): every estimate of a loader batch is first refined by point-to-point ICP on the
+    points the overlap gate indexes (lib/icp.py, one call per batch); without the flag nothing changes.
 Optional reference dependencies that are absent here (open3d, coloredlogs, matplotlib) are not needed.
 A run without --model uses random-init weights (no checkpoint download offline) and says so.
 
@@ -37,7 +39,8 @@ from lib.utils import (ensure_dir, read_trajectory, write_trajectory, read_traje
                        run_ransac_batch)
 from scripts.utils import make_pairwise_eval_data_loader  # noqa: E402
 from lib.checkpoints import CheckpointIO  # noqa: E402
-from lib.overlap import FragmentOverlap  # noqa: E402
+from lib.overlap import FragmentOverlap, _radius  # noqa: E402
+from lib.icp import icp_refine  # noqa: E402
 import lib.config as config  # noqa: E402
 
 SHORT_NAMES = {
@@ -83,10 +86,12 @@ def load_model(method, model_path, cfg_path=None):
 REC = 20
 
 
-def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overlap_threshold):
+def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overlap_threshold, icp=None):
     """benchmark:193-224 for one loader batch: the estimate of every pair (batched: OANet + Procrustes, or RANSAC,
     on the GPU), T_est = inv(estimate), the overlap gate -> float64 records [b, REC].  `bi` is the batch's index
-    in the whole evaluation (it seeds the RANSAC draws, so a batch gets the same draws on whichever rank it runs)."""
+    in the whole evaluation (it seeds the RANSAC draws, so a batch gets the same draws on whichever rank it runs).
+    icp = (max_dist, max_iters) (--icp): every estimate is first refined by point-to-point ICP on the points the
+    overlap gate indexes (lib.icp.icp_refine, one call per batch); the gate and the record use the refined one."""
     xs = batch["xs"][:, 0].numpy()
     if method == "RANSAC":
         T = _ransac(xs, seed=seed + bi)
@@ -101,11 +106,14 @@ def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overl
             T[:, :3, :3], T[:, :3, 3] = R, t
     # the overlap gate of every pair of the batch in one call (benchmark:217-220 scores one pair at a time on
     # the CPU): the batch's 2B clouds indexed once on the GPU, pair k = clouds (2k, 2k + 1)
-    T_est = np.linalg.inv(T)
     b = T.shape[0]
     clouds = [c for k in range(b) for c in (batch["xyz1"][k][0], batch["xyz2"][k][0])]
-    ratios = FragmentOverlap(clouds, method=overlap_method).ratios(
-        [[2 * k, 2 * k + 1] for k in range(b)], list(T_est)) if b else []
+    pairs = [[2 * k, 2 * k + 1] for k in range(b)]
+    fo = FragmentOverlap(clouds, method=overlap_method) if b else None
+    if icp is not None and b:
+        T = icp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1])["T"]
+    T_est = np.linalg.inv(T)
+    ratios = fo.ratios(pairs, list(T_est)) if b else []
     rec = np.zeros((b, REC), np.float64)
     for k in range(b):
         meta = batch["metadata"][k]
@@ -128,7 +136,7 @@ def _gather_records(rec, num_pairs, batch_size, world, pg=None):
 
 
 def estimate_trans_params(eval_data, source_path, dataset, scene_info, method, model, mutuals,
-                          overlap_method="FCGF", refine=False, seed=0, world=1, rank=0):
+                          overlap_method="FCGF", refine=False, seed=0, world=1, rank=0, icp=None):
     """benchmark:56-133 (method RANSAC) and :137-245 (learned filters), batched: writes traj.txt per scene.
     world > 1: `eval_data` is this rank's block of whole loader batches (lib.data.make_pairwise_eval_data_loader);
     the per-pair records are all-gathered and rank 0 writes the trajectories."""
@@ -145,8 +153,10 @@ def estimate_trans_params(eval_data, source_path, dataset, scene_info, method, m
     recs = []
     for bi, batch in enumerate(eval_data):
         timer.tic()
+        # the ICP settings travel as a keyword, and only when asked for: the positional signature is what stand-ins
+        # of _batch_records implement
         recs.append(_batch_records(batch, first // bsz + bi, method, model, refine, seed, overlap_method,
-                                   overlap_threshold))
+                                   overlap_threshold, **({} if icp is None else {"icp": icp})))
         timer.toc()
     rec = np.concatenate(recs) if recs else np.zeros((0, REC), np.float64)
     rec = _gather_records(rec, num_pairs, bsz, world)
@@ -173,11 +183,11 @@ def estimate_trans_params(eval_data, source_path, dataset, scene_info, method, m
 
 
 def evaluate_registration_performance(eval_data, source_path, dataset, scene_info, method, model, mutuals=False,
-                                      overlap_method="FCGF", refine=False, seed=0, world=1, rank=0):
+                                      overlap_method="FCGF", refine=False, seed=0, world=1, rank=0, icp=None):
     """benchmark:250-345: estimate (scenes without results), then the per-scene report; returns the summary.
     world > 1: rank 0 writes the trajectories and the report; every rank returns rank 0's summary."""
     estimate_trans_params(eval_data, source_path, dataset, scene_info, method, model, mutuals, overlap_method,
-                          refine, seed, world, rank)
+                          refine, seed, world, rank, icp)
     if world > 1:
         import torch.distributed as dist
         box = [_report(source_path, dataset, method, mutuals) if rank == 0 else None]
@@ -238,6 +248,11 @@ def parser():
     ap.add_argument("--config", default=None, type=str, help="filtering config YAML (default ./configs/pairwise_"
                     "registration/eval/<method>.yaml, as the reference reads it)")
     ap.add_argument("--seed", type=int, default=0, help="RANSAC draw stream seed")
+    ap.add_argument("--icp", action="store_true", help="refine every estimate by point-to-point ICP on the points of "
+                    "the overlap gate (voxel centroids for FCGF, raw points for 3DMatch) before it is scored")
+    ap.add_argument("--icp_max_dist", type=float, default=None, help="ICP correspondence distance, at most the "
+                    "overlap gate's radius for --overlap_method, which is the default")
+    ap.add_argument("--icp_iters", type=int, default=30, help="ICP iteration cap")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--dist_backend", default=None, choices=["nccl", "gloo"],
                     help="under torchrun (WORLD_SIZE > 1): the process group's backend (default nccl = RCCL on a GPU "
@@ -256,10 +271,17 @@ def main(argv=None):
     args.source_path = os.path.join(args.source_path, args.dataset)
     eval_data, scene_info = make_pairwise_eval_data_loader(args, num_workers=args.num_workers, world=world, rank=rank)
     model = None if args.method == "RANSAC" else load_model(args.method, args.model, args.config)
+    icp = None
+    if args.icp:
+        radius = _radius(args.overlap_method, 0.025)   # FragmentOverlap's default voxel size, as _batch_records builds it
+        icp = (radius if args.icp_max_dist is None else args.icp_max_dist, args.icp_iters)
+        if not 0.0 < icp[0] <= radius or icp[1] < 0:
+            raise ValueError("--icp_max_dist must lie in (0, %g] for --overlap_method %s, --icp_iters must not be "
+                             "negative" % (radius, args.overlap_method))
     with torch.no_grad():
         return evaluate_registration_performance(eval_data, args.source_path, args.dataset, scene_info, args.method,
                                                  model, args.mutuals, args.overlap_method, args.refine, args.seed,
-                                                 world, rank)
+                                                 world, rank, icp)
 
 
 if __name__ == "__main__":

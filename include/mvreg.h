@@ -285,7 +285,7 @@ int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_
                         size_t workspace_bytes, double* out_xyz, int64_t* out_off, mvr_stream_t stream);
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
- * for mvr_radius_overlap_count calls on the same points. */
+ * for mvr_radius_overlap_count and mvr_icp_refine calls on the same points. */
 size_t mvr_radius_index_bytes(int64_t M);
 int mvr_radius_index_build(const double* xyz, const int64_t* off, int B, int64_t M, double r, void* index,
                            size_t bytes, mvr_stream_t stream);
@@ -296,6 +296,41 @@ int mvr_radius_index_build(const double* xyz, const int64_t* off, int B, int64_t
 int mvr_radius_overlap_count(const void* index, size_t bytes, const double* xyz, const int64_t* off, int B,
                              int64_t M, const int64_t* pairs, const double* T, int P, int64_t max_points, double r,
                              int32_t* counts, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Point-to-point ICP refinement, batched over pairs, on a radius index (csrc/icp.hip).
+ * The reference stops at the coarse estimate, so this replaces nothing of it: it is the fine registration that
+ * Open3D's registration_icp (TransformationEstimationPointToPoint) does after the global estimate, restated from
+ * the maths; Open3D parity is unpinned.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`.
+ *   Pair p: source fragment pairs[2p], target fragment pairs[2p + 1], start T0[12p..] (3x4 row-major) with
+ *   x_target ~ R x_source + t (the estimators' convention; the inverse of mvr_radius_overlap_count's trans).
+ *   eval(T): every source point x maps to q = R x + t; its correspondence is the target point nearest to q (the
+ *   lowest row on equal distances), valid iff sqrt(ex*ex + ey*ey + ez*ez) < max_dist (strict, the expression of the
+ *   overlap gate).  n_corr = the valid ones, fitness = n_corr / n_source (0 for an empty source),
+ *   rmse = sqrt(sum d^2 / n_corr) (0 without correspondences).
+ *   Loop: state = eval(T0); up to max_iters times: stop with status bit 1 when n_corr < 3; T = the unweighted
+ *   Kabsch solution over the valid pairs on the original source points (det-corrected; no composition of
+ *   increments); new = eval(T); stop when |new.fitness - fitness| < tol_fitness and |new.rmse - rmse| < tol_rmse
+ *   (absolute differences; the new state is kept).  max_iters solves without that, and a tolerance > 0: status
+ *   bit 2 (also with max_iters == 0, a pure evaluation of T0: its cap of 0 solves is reached).  Both tolerances 0:
+ *   exactly max_iters solves, bit 2 never set.
+ *   Outputs per pair: T [P,12], fitness / rmse / n_corr of the returned T, iters = the solves done, status (bits:
+ *   1 fewer than 3 correspondences at an evaluation the loop looked at; 2 the cap; 4 an invalid pair: a fragment
+ *   index outside [0, B), offsets outside [0, M] or a non-finite T0 — then T = T0 copied bit for bit,
+ *   fitness = rmse = 0, iters = n_corr = 0).  trace [P, max_iters + 1, 2]: (fitness, rmse) of every evaluation, -1
+ *   in the rows after the last one.  n_corr, iters and trace may be NULL.
+ *   fp64 throughout; one workgroup per pair, every iteration inside the one launch, no workspace; a pair's outputs
+ *   are a function of the pair alone (bit-identical whatever the batch around it).
+ *   MVR_EINVAL, scalars first: negative P, M or max_iters; B <= 0 or B >= 32768; M >= 2^31; max_dist or
+ *   r_index <= 0; max_dist > r_index (the 27 cells around a query must cover its search ball); a negative
+ *   tolerance.  P == 0 then returns MVR_OK.  With P > 0: a NULL pairs, T0, T, fitness, rmse or status; with M > 0 a
+ *   NULL index, xyz or off, or index_bytes < mvr_radius_index_bytes(M).
+ * ---------------------------------------------------------------------- */
+int mvr_icp_refine(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
+                   double r_index, const int64_t* pairs, const double* T0, int P, double max_dist, int max_iters,
+                   double tol_fitness, double tol_rmse, double* T, double* fitness, double* rmse, int32_t* n_corr,
+                   int32_t* iters, int32_t* status, double* trace, mvr_stream_t stream);
 
 /* Farthest point sampling per fragment (Sampler 'fps', lib/layers.py:134-141 — pointnet2
  * furthest_point_sample semantics of oracle/fps.py: seed = first point, running min of squared

@@ -1,0 +1,120 @@
+"""Timing of the ICP refinement (csrc/icp.hip mvr_icp_refine) at the benchmark's scene shape: the 30-fragment synthetic
+scene's 435 pairs on its 0.025 m voxel centroids, ground-truth starts perturbed by 2 degrees / sigma 2 cm, max_dist =
+the index's cell (0.075 m), both tolerances 0 — 1 and 30 iterations, one pair alone, and for scale the scene's
+mvr_radius_overlap_count call on the same index (one 27-cell walk with early exit per query, both directions) and
+the host oracle (tests/icp_oracle.py: sklearn kd-tree + numpy SVD) on the first --host_pairs pairs.  HIP events around
+each call after a warm-up, median over --reps calls.
+A library built with another workgroup size (tools/build_variant.sh icp.hip icp512 -DMVR_ICP_THREADS=512,
+MVR_LIB=tools/vsp/icp512.so) times that variant.
+usage: python tools/icp_micro.py [--frags 30] [--reps 7] [--host_pairs 4]"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "3d_multiview_reg_amd"), os.path.join(ROOT, "tests"),
+          os.path.join(ROOT, "tests", "golden")):
+    sys.path.insert(0, p)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from lib import _native as N  # noqa: E402
+from lib.overlap import FragmentOverlap  # noqa: E402
+import icp_oracle as O  # noqa: E402
+from synth import synth_scene_fragments  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frags", type=int, default=30)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--host_pairs", type=int, default=4)
+    a = ap.parse_args()
+    d = torch.device("cuda")
+    frags, poses = synth_scene_fragments(n_frag=a.frags)
+    fo = FragmentOverlap(frags, "FCGF", 0.025)
+    sizes = np.diff(fo.off)
+    pairs = np.array([(i, j) for i in range(a.frags) for j in range(i + 1, a.frags)], np.int64)
+    rng = np.random.default_rng(0)
+    xyz = fo.xyz.cpu().numpy()
+    cent = [xyz[fo.off[b]:fo.off[b + 1]] for b in range(fo.B)]
+    T0 = np.empty((len(pairs), 4, 4))
+    for k, (i, j) in enumerate(pairs):
+        T = O.gt_transform(poses, i, j)
+        T0[k] = O.perturb(T, (cent[i] @ T[:3, :3].T + T[:3, 3]).mean(0), rng, 2.0, 0.02)
+    print("%s: %d fragments of %d..%d centroids (%d in all), %d pairs, cell %.3f m"
+          % (N.source_hash(), a.frags, sizes.min(), sizes.max(), fo.M, len(pairs), fo.r), flush=True)
+    L = N.lib()
+    gp_all = torch.from_numpy(pairs).to(d)
+    gT_all = torch.from_numpy(np.ascontiguousarray(T0[:, :3])).to(d)
+
+    def timed(run):
+        for _ in range(2):
+            run()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        ms.sort()
+        return ms
+
+    def bench(rows, iters, what):
+        P = len(rows)
+        gp, gT = gp_all[rows].contiguous(), gT_all[rows].contiguous()
+        T = torch.empty(P, 12, dtype=torch.float64, device=d)
+        fit, rm = (torch.empty(P, dtype=torch.float64, device=d) for _ in range(2))
+        nc, it, st = (torch.empty(P, dtype=torch.int32, device=d) for _ in range(3))
+
+        def run():
+            assert L.mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M,
+                                    fo.r, N.ptr(gp), N.ptr(gT), P, fo.r, iters, 0.0, 0.0, N.ptr(T), N.ptr(fit),
+                                    N.ptr(rm), N.ptr(nc), N.ptr(it), N.ptr(st), None, N.stream()) == 0
+        ms = timed(run)
+        print("icp %s, %d iterations: median %.3f ms (min %.3f, max %.3f, %d calls); fitness %.3f..%.3f, rmse mean "
+              "%.4f, status %s" % (what, iters, ms[len(ms) // 2], ms[0], ms[-1], a.reps, float(fit.min()),
+                                   float(fit.max()), float(rm.mean()), sorted(set(st.tolist()))), flush=True)
+        return ms[len(ms) // 2]
+
+    every = torch.arange(len(pairs), device=d)
+    t0 = bench(every, 0, "%d pairs" % len(pairs))
+    t1 = bench(every, 1, "%d pairs" % len(pairs))
+    t30 = bench(every, 30, "%d pairs" % len(pairs))
+    one = bench(every[:1], 30, "pair (0, 1) alone")
+    print("per evaluation: %.3f ms over the scene ((30 - 1 iterations) / 29), %.3f ms for the pair alone"
+          % ((t30 - t1) / 29.0, one / 31.0), flush=True)
+
+    # the overlap gate on the same index and transforms: both directions of every pair, early exit at the first hit
+    Tg = np.empty((len(pairs), 2, 3, 4))
+    Tg[:, 0], Tg[:, 1] = T0[:, :3], np.linalg.inv(T0)[:, :3]
+    gTg = torch.from_numpy(Tg).to(d)
+    cnt = torch.empty(len(pairs), 2, dtype=torch.int32, device=d)
+
+    def gate():
+        assert L.mvr_radius_overlap_count(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
+                                          fo.M, N.ptr(gp_all), N.ptr(gTg), len(pairs), fo.max_points, fo.r,
+                                          N.ptr(cnt), N.stream()) == 0
+    ms = timed(gate)
+    print("mvr_radius_overlap_count, %d pairs x 2 directions: median %.3f ms (min %.3f, max %.3f); the evaluation "
+          "alone (0 iterations) %.3f ms" % (len(pairs), ms[len(ms) // 2], ms[0], ms[-1], t0), flush=True)
+
+    host = []
+    for k in range(min(a.host_pairs, len(pairs))):
+        i, j = pairs[k]
+        t = time.perf_counter()
+        r = O.icp(cent[i], cent[j], T0[k], fo.r, 30, 0.0, 0.0)
+        host.append((time.perf_counter() - t) * 1e3)
+        assert r["iters"] == 30
+    host.sort()
+    if host:
+        print("host oracle (kd-tree + SVD), 30 iterations: median %.1f ms per pair over %d pairs -> about %.0f ms for "
+              "%d pairs one after the other (extrapolated); the GPU's pair alone %.3f ms"
+              % (host[len(host) // 2], len(host), host[len(host) // 2] * len(pairs), len(pairs), one), flush=True)
+
+
+if __name__ == "__main__":
+    main()
