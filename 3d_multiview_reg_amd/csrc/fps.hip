@@ -234,14 +234,13 @@ extern "C" int mvr_fps(const float* xyz, const int64_t* offsets, const int64_t* 
     MVR_CHECK_LAUNCH();                                                                                \
     return MVR_OK;                                                                                     \
   }
-  // 1024 threads: 4 VGPRs per point within the 128 a 1024-thread workgroup allows; 512 threads: 256
+  // 1024 threads: 4 VGPRs per point within the 128 a 1024-thread workgroup allows: 24 points per thread at the
+  // most (24,576 per fragment); larger fragments re-read their coordinates from L2 (fps_kernel)
   MVR_FPSR(1024, 4)
   MVR_FPSR(1024, 8)
   MVR_FPSR(1024, 16)
   MVR_FPSR(1024, 20)
   MVR_FPSR(1024, 24)
-  MVR_FPSR(768, 32)
-  MVR_FPSR(512, 48)
 #undef MVR_FPSR
   MVR_FPS(1024, 64, false)
   MVR_FPS(512, 160, false)

@@ -44,15 +44,20 @@ __global__ void frag_min_kernel(const float* __restrict__ xyz, const int64_t* __
   if (threadIdx.x < 3) minb[3 * b + threadIdx.x] = red[threadIdx.x][0];
 }
 
-// Open3D: ref = (p - (min_bound - v/2)) / v; index = floor(ref)   (fp64)
+// Open3D: ref = (p - (min_bound - v/2)) / v; index = floor(ref)   (fp64).  The index is >= 0 by construction; one
+// that does not fit pack_key's OV_BITS field would be masked into another voxel of the fragment, so it marks the
+// call as over range instead (out_off[B] = OV_OVER_RANGE, turned into the documented -1 by fix_offsets_kernel).
+constexpr int64_t OV_OVER_RANGE = -2;
 __global__ void voxel_key_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ off, int B, int64_t n,
                                  const double* __restrict__ minb, double v, uint64_t* keys, uint64_t* keys2,
-                                 int32_t* idx) {
+                                 int32_t* idx, int64_t* out_off) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int b = frag_of(off, B, i);
   int64_t c[3];
   for (int d = 0; d < 3; ++d) c[d] = (int64_t)floor(((double)xyz[3 * i + d] - (minb[3 * b + d] - v * 0.5)) / v);
+  for (int d = 0; d < 3; ++d)
+    if (c[d] < 0 || c[d] >= ((int64_t)1 << OV_BITS)) out_off[B] = OV_OVER_RANGE;   // same value from every writer
   const uint64_t k = pack_key(b, c[0], c[1], c[2]);
   keys[i] = k;
   keys2[i] = k;
@@ -93,9 +98,11 @@ __global__ void centroid_kernel(const float* __restrict__ xyz, const uint64_t* _
 }
 
 __global__ void fix_offsets_kernel(int64_t* out_off, int B, const int32_t* head, const int32_t* pos, int64_t n) {
+  const bool over = out_off[B] == OV_OVER_RANGE;
   out_off[B] = n > 0 ? (int64_t)pos[n - 1] + head[n - 1] : 0;
   for (int b = B - 1; b >= 0; --b)
     if (out_off[b] < 0) out_off[b] = out_off[b + 1];   // fragments without points
+  if (over) out_off[B] = -1;   // a voxel index left the key's field: the centroids are not valid (mvreg.h)
 }
 
 __global__ void fill_i64_kernel(int64_t* p, int64_t n, int64_t v) {
@@ -223,7 +230,7 @@ extern "C" int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, in
   hipLaunchKernelGGL(fill_i64_kernel, dim3(nb(B + 1)), dim3(256), 0, s, out_off, (int64_t)B + 1, (int64_t)-1);
   hipLaunchKernelGGL(frag_min_kernel, dim3(B), dim3(256), 0, s, xyz, frag_off, minb);
   hipLaunchKernelGGL(voxel_key_kernel, dim3(nb(n)), dim3(256), 0, s, xyz, frag_off, B, n, minb, voxel, rw.ka, kin,
-                     rw.va);
+                     rw.va, out_off);
   int rc = radix_sort(rw, key_bits(B), vout, s);   // stable: a voxel's points stay in input order
   if (rc != MVR_OK) return rc;
   hipLaunchKernelGGL(gather_keys_kernel, dim3(nb(n)), dim3(256), 0, s, kin, vout, n, kout);

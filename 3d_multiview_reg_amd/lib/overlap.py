@@ -16,6 +16,7 @@ import torch
 from lib import _native as N
 
 R_3DMATCH = 0.05
+MAX_VOXELS_PER_AXIS = 65535   # largest 16-bit voxel index of mvr_voxel_centroids (include/mvreg.h)
 
 
 def _radius(method, voxel_size):
@@ -53,6 +54,10 @@ class FragmentOverlap(object):
             N.check(L.mvr_voxel_centroids(N.ptr(xyz), N.ptr(off_dev), B, n, self.voxel_size, N.ptr(ws), ws_b,
                                           N.ptr(cent), N.ptr(off), N.stream()), "mvr_voxel_centroids")
             self.off = off.cpu().numpy()
+            if self.off[-1] < 0:    # set on the device by mvr_voxel_centroids: no synchronisation beyond this copy
+                raise ValueError("FragmentOverlap: a fragment spans more than %d voxels of size %g along an axis "
+                                 "(voxel indices are 16-bit, so an extent of at most %g); use a larger voxel_size"
+                                 % (MAX_VOXELS_PER_AXIS, self.voxel_size, MAX_VOXELS_PER_AXIS * self.voxel_size))
             self.xyz = cent[:int(self.off[-1])].contiguous()
         else:
             self.xyz = torch.cat([p.reshape(-1, 3).to(dev, torch.float64) for p in pts]).contiguous()
@@ -86,11 +91,15 @@ class FragmentOverlap(object):
         return cnt[:P].cpu().numpy()
 
     def ratios(self, pairs, trans):
-        """-> float64 [P]: max of the two overlap ratios (utils.py:779-786)."""
+        """-> float64 [P]: max of the two overlap ratios (utils.py:779-786).  A pair with an empty fragment has no
+        overlap: 0.0 (the reference divides by zero there)."""
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         c = self.counts(pairs, trans).astype(np.float64)
         n = np.diff(self.off).astype(np.float64)
-        return np.maximum(c[:, 0] / n[pairs[:, 0]], c[:, 1] / n[pairs[:, 1]])
+        ni, nj = n[pairs[:, 0]], n[pairs[:, 1]]
+        ok = (ni > 0) & (nj > 0)
+        # counts are 0 beside an empty fragment, so a denominator of 1 there gives the 0.0
+        return np.where(ok, np.maximum(c[:, 0] / np.where(ok, ni, 1.0), c[:, 1] / np.where(ok, nj, 1.0)), 0.0)
 
 
 def overlap_ratio(pc_i, pc_j, trans, method="3DMatch", voxel_size=0.025):

@@ -278,14 +278,25 @@ int mvr_xs_to_channels(const float* xs, int64_t xs_pstride, int64_t xs_nstride, 
  * Open3D VoxelDownSample restated: per fragment b (xyz float32 [n,3], frag_off [B+1] device int64),
  * voxel index floor((p - (min_b - v/2)) / v) in fp64, centroid = fp64 sum of the voxel's points in input
  * order / count.  out_xyz fp64 [n,3] capacity (voxels of a fragment contiguous, fragments in order),
- * out_off [B+1] (device).  Voxel coordinates must stay below 65536 per axis; B <= 4096.
+ * out_off [B+1] (device).  B <= 4096.
+ * Coordinate limit: a voxel index is kept in 16 bits per axis, so every fragment must satisfy
+ * floor((max - min) / v + 0.5) <= 65535 along each axis, i.e. an extent below about 65535.5 v (1,638 m at
+ * v = 0.025, 65.5 m at v = 0.001).  The index is relative to the fragment's own minimum, so where a fragment lies
+ * does not matter.  A fragment beyond the limit is detected on the device without a synchronisation: the call still
+ * returns MVR_OK and out_off[B] holds -1 instead of the voxel total; out_off[0..B-1] and out_xyz are then not
+ * meaningful (nothing is written out of bounds).  lib.overlap.FragmentOverlap raises ValueError on it.
  * ---------------------------------------------------------------------- */
 size_t mvr_voxel_centroids_workspace_bytes(int64_t n);
 int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel, void* workspace,
                         size_t workspace_bytes, double* out_xyz, int64_t* out_off, mvr_stream_t stream);
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
- * for mvr_radius_overlap_count and mvr_icp_refine calls on the same points. */
+ * for mvr_radius_overlap_count and mvr_icp_refine calls on the same points.  B < 32768.
+ * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
+ * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
+ * cells of a fragment form one run of the sorted order under one hash entry, a query walks the whole run, and
+ * every candidate still passes the fp64 distance test, so a far point is never matched and a near one never
+ * missed; the cost is the longer run.  The fragment index is kept above the 48 coordinate bits and never aliases. */
 size_t mvr_radius_index_bytes(int64_t M);
 int mvr_radius_index_build(const double* xyz, const int64_t* off, int B, int64_t M, double r, void* index,
                            size_t bytes, mvr_stream_t stream);
@@ -336,7 +347,9 @@ int mvr_icp_refine(const void* index, size_t index_bytes, const double* xyz, con
  * furthest_point_sample semantics of oracle/fps.py: seed = first point, running min of squared
  * distances, first maximum on ties).  xyz [sum n][3] with fragment row offsets (device `offsets`
  * and the same values on the host, B+1 entries); idx_out [B][m] int64 global rows.  n >= m for
- * every fragment, n <= 81920. */
+ * every fragment (MVR_EINVAL otherwise: FPS draws m distinct points).  Limit: n <= 81,920 points per fragment
+ * (512 threads x 160 running distances in registers, the largest instance); a larger fragment is MVR_EINVAL.
+ * The kernel is chosen by the largest fragment of the batch and smaller fragments ride in it. */
 int mvr_fps(const float* xyz, const int64_t* offsets, const int64_t* offsets_host, int B, int m, int64_t* idx_out,
             mvr_stream_t stream);
 

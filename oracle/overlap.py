@@ -25,8 +25,9 @@ def voxel_down_sample(xyz, voxel):
     return s / cnt[:, None]
 
 
-def overlap_counts(pc_i, pc_j, trans, method="3DMatch", voxel_size=0.025):
-    """-> (matching01, matching10, n_i, n_j) as in utils.py:734-776."""
+def overlap_counts(pc_i, pc_j, trans, method="3DMatch", voxel_size=0.025, radius=None):
+    """-> (matching01, matching10, n_i, n_j) as in utils.py:734-776.  radius: the match radius instead of the
+    method's (the `radius=` of lib.overlap.FragmentOverlap; not in the reference)."""
     from sklearn.neighbors import NearestNeighbors
     trans = np.asarray(trans, dtype=np.float64)
     trans_inv = np.linalg.inv(trans)
@@ -39,6 +40,8 @@ def overlap_counts(pc_i, pc_j, trans, method="3DMatch", voxel_size=0.025):
         r = 0.05
     else:
         raise ValueError(method)
+    if radius is not None:
+        r = float(radius)
     pc_i_t = (trans_inv[0:3, 0:3] @ pc_i.T + trans_inv[0:3, 3].reshape(-1, 1)).T
     pc_j_t = (trans[0:3, 0:3] @ pc_j.T + trans[0:3, 3].reshape(-1, 1)).T
     neigh = NearestNeighbors(n_neighbors=1, algorithm="kd_tree")
