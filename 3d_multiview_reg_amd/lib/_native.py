@@ -104,6 +104,11 @@ _SIGS = {
     "mvr_icp_refine": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_int,
                                ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_vp, c_vp]),
+    "mvr_estimate_normals": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_vp,
+                                     c_vp, c_vp, c_vp]),
+    "mvr_icp_refine_plane": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_int,
+                                     ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp]),
     "mvr_hash_table_bytes": (c_size, [c_i64]),
     "mvr_voxelize_workspace_bytes": (c_size, [c_i64]),
     "mvr_voxelize_hint_workspace_bytes": (c_size, [c_i64, c_i64]),

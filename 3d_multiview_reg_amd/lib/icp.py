@@ -1,5 +1,6 @@
-"""Fine registration: batched point-to-point ICP on the fragments' own points (csrc/icp.hip mvr_icp_refine; the
-semantics are in DESIGN.md 4.19 and include/mvreg.h).
+"""Fine registration: batched ICP on the fragments' own points, point-to-point (csrc/icp.hip mvr_icp_refine,
+DESIGN.md 4.19) or point-to-plane on normals (csrc/icp_plane.hip mvr_icp_refine_plane); the semantics
+are in include/mvreg.h.
 
 The reference stops at the coarse estimate (Procrustes or RANSAC over the sampled correspondences); its users
 follow it with Open3D's `registration_icp`.  `icp_refine` does that for every pair of a scene in one launch, on the
@@ -15,6 +16,8 @@ import torch
 from lib import _native as N
 
 STATUS_FEW_CORRESPONDENCES, STATUS_ITERATION_CAP, STATUS_INVALID_PAIR = 1, 2, 4
+STATUS_DEGENERATE = 8     # point-to-plane only: the 6 x 6 system is not positive definite to working precision
+METHODS = ("point_to_point", "point_to_plane")
 
 
 def _check_settings(name, max_dist, max_iters, tol_fitness, tol_rmse):
@@ -26,19 +29,28 @@ def _check_settings(name, max_dist, max_iters, tol_fitness, tol_rmse):
         raise ValueError("%s: the tolerances must not be negative" % name)
 
 
-def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, return_trace=False):
+def _check_method(name, method):
+    if method not in METHODS:
+        raise ValueError("%s: method must be one of %s, not %r" % (name, ", ".join(METHODS), method))
+
+
+def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, return_trace=False,
+               method="point_to_point"):
     """Refine the transform of every pair on the points of `fo` (a lib.overlap.FragmentOverlap: its centroids for
     method 'FCGF', its raw points for '3DMatch').
 
     pairs [P,2] (source, target) fragment indices; T_init [P,4,4] or [P,3,4], numpy or torch, any float dtype;
     max_dist: the correspondence distance, at most fo.r (None: fo.r).  Stops after max_iters solves, or when fitness
     and rmse both change by less than their tolerances (absolute); both tolerances 0 run exactly max_iters.
+    method 'point_to_plane' minimises the distances along the target's normals instead: fo.normals (fp64 [M,3] on the
+    device, from fo.estimate_normals() or assigned by the caller) must be there; their sign does not matter.
     Returns a dict of fp64 T [P,4,4], fp64 fitness / rmse [P], int32 n_corr / iters / status [P] (STATUS_* bits) and,
     with return_trace, fp64 trace [P, max_iters + 1, 2]: (fitness, rmse) of every evaluation, -1 after the last.
     The outputs stay on the device when T_init was on the device; otherwise they come back on the host (numpy for
     numpy inputs)."""
     max_dist = float(fo.r if max_dist is None else max_dist)
     _check_settings("icp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
+    _check_method("icp_refine", method)
     if max_dist > fo.r:
         raise ValueError("icp_refine: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
                          "radius >= max_dist)" % (max_dist, fo.r))
@@ -49,6 +61,15 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     ij = torch.as_tensor(pairs)
     if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
         raise ValueError("icp_refine: pairs must be [P,2] with one row per transform")
+    plane = method == "point_to_plane"
+    if plane:
+        nrm = getattr(fo, "normals", None)
+        if nrm is None:
+            raise ValueError("icp_refine: method 'point_to_plane' needs fo.normals (call fo.estimate_normals())")
+        if not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64 or \
+                nrm.device != fo.xyz.device or not nrm.is_contiguous():
+            raise ValueError("icp_refine: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
+                             % fo.M)
     N.require_hip()
     on_dev = Tin.device.type == "cuda"
     dev = fo.device
@@ -59,10 +80,14 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
     n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
     trace = torch.empty(P, rows, 2, dtype=torch.float64, device=dev) if return_trace else None
-    N.check(N.lib().mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M,
-                                   fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, int(max_iters), float(tol_fitness),
-                                   float(tol_rmse), N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr),
-                                   N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream()), "mvr_icp_refine")
+    tail = (fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, int(max_iters), float(tol_fitness), float(tol_rmse), N.ptr(T),
+            N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream())
+    if plane:
+        N.check(N.lib().mvr_icp_refine_plane(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals),
+                                             N.ptr(fo.off_dev), fo.B, fo.M, *tail), "mvr_icp_refine_plane")
+    else:
+        N.check(N.lib().mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
+                                       fo.M, *tail), "mvr_icp_refine")
     T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
     T4[:, :3], T4[:, 3, 3] = T, 1.0
     out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
@@ -75,14 +100,20 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     return out
 
 
-def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, **kw):
+def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="point_to_point", normal_radius=None,
+             **kw):
     """One pair in the shape of Open3D's registration_icp(source, target, max_correspondence_distance, init):
     src_xyz [n,3], tgt_xyz [m,3], T_init [4,4] or [3,4] with x_target ~ T x_source.  voxel_size None: the raw points;
     a value: Open3D-style voxel centroids of both clouds (lib.overlap).  **kw: max_iters, tol_fitness, tol_rmse,
-    return_trace of icp_refine.  Returns icp_refine's dict without the leading [P]."""
+    return_trace of icp_refine.  method 'point_to_plane': the normals are estimated here over normal_radius (None:
+    max_dist) on an index of cell max(max_dist, normal_radius); TransformationEstimationPointToPlane after
+    estimate_normals(KDTreeSearchParamRadius(normal_radius)).  Returns icp_refine's dict without the leading [P]."""
     from lib.overlap import FragmentOverlap
     _check_settings("icp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
                     kw.get("tol_rmse", 0.0))
+    _check_method("icp_pair", method)
+    if normal_radius is not None and not normal_radius > 0.0:
+        raise ValueError("icp_pair: normal_radius must be positive")
     if voxel_size is not None and not voxel_size > 0.0:
         raise ValueError("icp_pair: voxel_size must be positive")
     for name, x in (("src_xyz", src_xyz), ("tgt_xyz", tgt_xyz)):
@@ -92,10 +123,15 @@ def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, **kw):
     Tin = torch.as_tensor(T_init)
     if tuple(Tin.shape) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
         raise ValueError("icp_pair: T_init must be a float [4,4] or [3,4]")
+    plane = method == "point_to_plane"
+    nr = max_dist if normal_radius is None else normal_radius
+    cell = max(max_dist, nr) if plane else max_dist      # the index's cells cover the search ball and the normals'
     if voxel_size is None:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=max_dist)
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell)
     else:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=max_dist)
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell)
+    if plane:
+        fo.estimate_normals(nr)
     T0 = T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None]
-    out = icp_refine(fo, [[0, 1]], T0, max_dist, **kw)
+    out = icp_refine(fo, [[0, 1]], T0, max_dist, method=method, **kw)
     return {k: v[0] for k, v in out.items()}

@@ -70,6 +70,32 @@ class FragmentOverlap(object):
         N.check(L.mvr_radius_index_build(N.ptr(self.xyz), N.ptr(self.off_dev), B, self.M, self.r, N.ptr(self.index),
                                          ib, N.stream()), "mvr_radius_index_build")
         self.device = dev
+        self.normals = self.n_nbr = None   # set by estimate_normals, or normals assigned by the caller
+
+    def estimate_normals(self, radius=None, viewpoints=None):
+        """Per-point normals of every fragment (csrc/normals.hip mvr_estimate_normals: Open3D's estimate_normals with
+        a radius search, restated): the eigenvector of the smallest eigenvalue of the covariance of the points of the
+        same fragment closer than `radius` (None: fo.r; at most fo.r), (0, 0, 1) below three of them.
+        viewpoints [B,3] (one per fragment): normals point towards them; None: the sign is unspecified.
+        Stores and returns fo.normals (fp64 [M,3], device, the row order of fo.xyz); fo.n_nbr (int32 [M]) holds the
+        neighbour counts."""
+        radius = float(self.r if radius is None else radius)
+        if not 0.0 < radius <= self.r:
+            raise ValueError("estimate_normals: radius %g must lie in (0, %g], the index's cell size (build the "
+                             "FragmentOverlap with radius >= it)" % (radius, self.r))
+        vp = None
+        if viewpoints is not None:
+            vp = torch.as_tensor(np.asarray(viewpoints) if not torch.is_tensor(viewpoints) else viewpoints)
+            if tuple(vp.shape) != (self.B, 3) or not vp.is_floating_point():
+                raise ValueError("estimate_normals: viewpoints must be a float [%d,3], one per fragment" % self.B)
+            vp = vp.to(self.device, torch.float64).contiguous()
+        normals = torch.empty(self.M, 3, dtype=torch.float64, device=self.device)
+        n_nbr = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        N.check(N.lib().mvr_estimate_normals(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz),
+                                             N.ptr(self.off_dev), self.B, self.M, self.r, radius, N.ptr(vp),
+                                             N.ptr(normals), N.ptr(n_nbr), N.stream()), "mvr_estimate_normals")
+        self.normals, self.n_nbr = normals, n_nbr
+        return normals
 
     def counts(self, pairs, trans):
         """pairs [P, 2] fragment indices, trans [P, 4, 4] (the `trans` argument of the reference) ->

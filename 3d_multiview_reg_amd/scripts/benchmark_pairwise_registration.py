@@ -13,6 +13,7 @@ report), with the per-pair host loop replaced by batched GPU calls:
     errors per scene against gt.log / gt.info (benchmark:250-345);
   * `--icp` (not in the reference): every estimate of a loader batch is first refined by point-to-point ICP on the
     points the overlap gate indexes (lib/icp.py, one call per batch); without the flag nothing changes.
+    `--icp_method point_to_plane` minimises along normals estimated on those points over `--icp_normal_radius`.
 Optional reference dependencies that are absent here (open3d, coloredlogs, matplotlib) are not needed.
 A run without --model uses random-init weights (no checkpoint download offline) and says so.
 
@@ -91,7 +92,9 @@ def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overl
     on the GPU), T_est = inv(estimate), the overlap gate -> float64 records [b, REC].  `bi` is the batch's index
     in the whole evaluation (it seeds the RANSAC draws, so a batch gets the same draws on whichever rank it runs).
     icp = (max_dist, max_iters) (--icp): every estimate is first refined by point-to-point ICP on the points the
-    overlap gate indexes (lib.icp.icp_refine, one call per batch); the gate and the record use the refined one."""
+    overlap gate indexes (lib.icp.icp_refine, one call per batch); the gate and the record use the refined one.
+    icp = (max_dist, max_iters, 'point_to_plane', normal_radius): by point-to-plane ICP, on normals estimated on
+    those points over normal_radius."""
     xs = batch["xs"][:, 0].numpy()
     if method == "RANSAC":
         T = _ransac(xs, seed=seed + bi)
@@ -111,7 +114,10 @@ def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overl
     pairs = [[2 * k, 2 * k + 1] for k in range(b)]
     fo = FragmentOverlap(clouds, method=overlap_method) if b else None
     if icp is not None and b:
-        T = icp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1])["T"]
+        if len(icp) > 2:
+            fo.estimate_normals(icp[3])
+        T = icp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1],
+                       **({"method": icp[2]} if len(icp) > 2 else {}))["T"]
     T_est = np.linalg.inv(T)
     ratios = fo.ratios(pairs, list(T_est)) if b else []
     rec = np.zeros((b, REC), np.float64)
@@ -253,6 +259,10 @@ def parser():
     ap.add_argument("--icp_max_dist", type=float, default=None, help="ICP correspondence distance, at most the "
                     "overlap gate's radius for --overlap_method, which is the default")
     ap.add_argument("--icp_iters", type=int, default=30, help="ICP iteration cap")
+    ap.add_argument("--icp_method", default="point_to_point", choices=["point_to_point", "point_to_plane"],
+                    help="what --icp minimises: point distances, or distances along the target's normals")
+    ap.add_argument("--icp_normal_radius", type=float, default=None, help="point_to_plane: the radius of the normal "
+                    "estimation, at most the overlap gate's radius for --overlap_method, which is the default")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--dist_backend", default=None, choices=["nccl", "gloo"],
                     help="under torchrun (WORLD_SIZE > 1): the process group's backend (default nccl = RCCL on a GPU "
@@ -278,6 +288,11 @@ def main(argv=None):
         if not 0.0 < icp[0] <= radius or icp[1] < 0:
             raise ValueError("--icp_max_dist must lie in (0, %g] for --overlap_method %s, --icp_iters must not be "
                              "negative" % (radius, args.overlap_method))
+        if args.icp_method == "point_to_plane":   # the default method keeps the two settings it always had
+            icp += ("point_to_plane", radius if args.icp_normal_radius is None else args.icp_normal_radius)
+            if not 0.0 < icp[3] <= radius:
+                raise ValueError("--icp_normal_radius must lie in (0, %g] for --overlap_method %s"
+                                 % (radius, args.overlap_method))
     with torch.no_grad():
         return evaluate_registration_performance(eval_data, args.source_path, args.dataset, scene_info, args.method,
                                                  model, args.mutuals, args.overlap_method, args.refine, args.seed,

@@ -291,7 +291,8 @@ int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_
                         size_t workspace_bytes, double* out_xyz, int64_t* out_off, mvr_stream_t stream);
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
- * for mvr_radius_overlap_count and mvr_icp_refine calls on the same points.  B < 32768.
+ * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals and mvr_icp_refine_plane calls on the same
+ * points.  B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
  * cells of a fragment form one run of the sorted order under one hash entry, a query walks the whole run, and
@@ -342,6 +343,55 @@ int mvr_icp_refine(const void* index, size_t index_bytes, const double* xyz, con
                    double r_index, const int64_t* pairs, const double* T0, int P, double max_dist, int max_iters,
                    double tol_fitness, double tol_rmse, double* T, double* fitness, double* rmse, int32_t* n_corr,
                    int32_t* iters, int32_t* status, double* trace, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Per-point normals on a radius index (csrc/normals.hip): Open3D's
+ * estimate_normals(KDTreeSearchParamRadius(radius)) restated from the maths; Open3D parity is unpinned.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`.
+ *   The neighbours of point i are the points of its own fragment with sqrt(ex*ex + ey*ey + ez*ez) < radius (strict,
+ *   the expression of the overlap gate), e = x_j - x_i; the point itself is one of them.  n_nbr[i] = their number
+ *   (n_nbr may be NULL).  Fewer than 3: the normal is (0, 0, 1).  Otherwise C = mean(e e^T) - mean(e) mean(e)^T over
+ *   the neighbours and the normal is the unit eigenvector of C's smallest eigenvalue (cyclic symmetric Jacobi; on
+ *   exactly equal eigenvalues the later axis of the decomposition).  A zero row and column of C keep their axis
+ *   exactly: a fragment in the plane z = 0 gets exactly (0, 0, +-1).
+ *   Sign: with viewpoints [B,3] (one per fragment, device) the normal of a point p of fragment b is flipped so that
+ *   n . (v_b - p) >= 0.  With viewpoints == NULL the sign is whatever the eigen-solve leaves: unspecified, and it
+ *   may differ between builds; mvr_icp_refine_plane does not depend on it.
+ *   normals [M,3] and n_nbr [M] in the row order of xyz; every row is written.  fp64 throughout; one thread per point,
+ *   no atomics, no workspace; a point's outputs are a function of its fragment alone.
+ *   MVR_EINVAL, scalars first: negative M or M >= 2^31; B <= 0 or B >= 32768; radius or r_index <= 0;
+ *   radius > r_index (the 27 cells around a point must cover its ball).  M == 0 then returns MVR_OK.  With M > 0: a
+ *   NULL index, xyz, off or normals, or index_bytes < mvr_radius_index_bytes(M).
+ * ---------------------------------------------------------------------- */
+int mvr_estimate_normals(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
+                         int64_t M, double r_index, double radius, const double* viewpoints, double* normals,
+                         int32_t* n_nbr, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Point-to-plane ICP refinement, batched over pairs (csrc/icp_plane.hip): the loop of Open3D's
+ * registration_icp with TransformationEstimationPointToPlane, restated from the maths; Open3D parity is unpinned.
+ * The arguments are those of mvr_icp_refine plus normals [M,3] (the row order of xyz; unit length is the caller's
+ * business, mvr_estimate_normals gives it; their sign does not matter: a and b below change sign together).
+ *   eval(T), fitness, rmse, n_corr: exactly mvr_icp_refine's (Euclidean distances), so the two methods' figures
+ *   compare.
+ *   Loop: state = eval(T0); up to max_iters times: stop with status bit 1 when n_corr < 6.  Over the valid pairs
+ *   q = T x, y its match, n the normal of y, c = the target fragment's first point (a per-pair origin: the cross
+ *   products then have the size of the fragment, not of its distance from the world origin):
+ *   a = [(q - c) x n, n], b = (q - y) . n; solve (sum a a^T) xi = -sum a b by Cholesky.  A pivot that fails
+ *   pivot > 1e-12 max_i H_ii (a NaN fails it too) stops the loop with status bit 8, T kept, iters not counted.
+ *   Otherwise D = [R_inc | xi[3:6] + c - R_inc c], R_inc = Rz(xi[2]) Ry(xi[1]) Rx(xi[0]), and T <- D T: increments
+ *   compose and T is not re-orthonormalised.  new = eval(T); the stopping rule, bit 2, bit 4, the trace, the NULL
+ *   outputs and the invalid-pair behaviour are mvr_icp_refine's.
+ *   Status bits: 1 fewer than 6 correspondences; 2 the cap; 4 an invalid pair; 8 a degenerate system.
+ *   One workgroup per pair, every iteration inside the one launch, no atomics, no workspace; a pair's outputs are a
+ *   function of the pair alone.
+ *   MVR_EINVAL: the rules of mvr_icp_refine; with P > 0 and M > 0 also a NULL normals.
+ * ---------------------------------------------------------------------- */
+int mvr_icp_refine_plane(const void* index, size_t index_bytes, const double* xyz, const double* normals,
+                         const int64_t* off, int B, int64_t M, double r_index, const int64_t* pairs, const double* T0,
+                         int P, double max_dist, int max_iters, double tol_fitness, double tol_rmse, double* T,
+                         double* fitness, double* rmse, int32_t* n_corr, int32_t* iters, int32_t* status,
+                         double* trace, mvr_stream_t stream);
 
 /* Farthest point sampling per fragment (Sampler 'fps', lib/layers.py:134-141 — pointnet2
  * furthest_point_sample semantics of oracle/fps.py: seed = first point, running min of squared

@@ -1,12 +1,15 @@
-"""Timing of the ICP refinement (csrc/icp.hip mvr_icp_refine) at the benchmark's scene shape: the 30-fragment synthetic
+"""Timing of the ICP refinement (csrc/icp.hip mvr_icp_refine, or with --method point_to_plane csrc/icp_plane.hip
+mvr_icp_refine_plane after csrc/normals.hip mvr_estimate_normals) at the benchmark's scene shape: the 30-fragment synthetic
 scene's 435 pairs on its 0.025 m voxel centroids, ground-truth starts perturbed by 2 degrees / sigma 2 cm, max_dist =
 the index's cell (0.075 m), both tolerances 0 — 1 and 30 iterations, one pair alone, and for scale the scene's
 mvr_radius_overlap_count call on the same index (one 27-cell walk with early exit per query, both directions) and
 the host oracle (tests/icp_oracle.py: sklearn kd-tree + numpy SVD) on the first --host_pairs pairs.  HIP events around
-each call after a warm-up, median over --reps calls.
-A library built with another workgroup size (tools/build_variant.sh icp.hip icp512 -DMVR_ICP_THREADS=512,
+each call after a warm-up, median over --reps calls.  point_to_plane also times the normal estimation (radius = the
+cell), and both methods report the iterations to convergence at tolerances 1e-6 from the same starts.
+A library built with another workgroup size (tools/build_variant.sh icp.hip icp512 -DMVR_ICP_THREADS=512, or
+icp_plane.hip plane512 -DMVR_ICP_PLANE_THREADS=512, normals.hip nrm256 -DMVR_NORMALS_THREADS=256;
 MVR_LIB=tools/vsp/icp512.so) times that variant.
-usage: python tools/icp_micro.py [--frags 30] [--reps 7] [--host_pairs 4]"""
+usage: python tools/icp_micro.py [--method point_to_point|point_to_plane] [--frags 30] [--reps 7] [--host_pairs 4]"""
 import argparse
 import os
 import sys
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--frags", type=int, default=30)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--host_pairs", type=int, default=4)
+    ap.add_argument("--method", default="point_to_point", choices=["point_to_point", "point_to_plane"])
     a = ap.parse_args()
     d = torch.device("cuda")
     frags, poses = synth_scene_fragments(n_frag=a.frags)
@@ -63,18 +67,43 @@ def main():
         ms.sort()
         return ms
 
-    def bench(rows, iters, what):
+    plane = a.method == "point_to_plane"
+    if plane:
+        nrm = torch.empty(fo.M, 3, dtype=torch.float64, device=d)
+        nnb = torch.empty(fo.M, dtype=torch.int32, device=d)
+
+        def normals():
+            assert L.mvr_estimate_normals(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
+                                          fo.M, fo.r, fo.r, None, N.ptr(nrm), N.ptr(nnb), N.stream()) == 0
+        ms = timed(normals)
+        print("mvr_estimate_normals, %d points, radius %.3f: median %.3f ms (min %.3f, max %.3f); neighbours %d..%d"
+              % (fo.M, fo.r, ms[len(ms) // 2], ms[0], ms[-1], int(nnb.min()), int(nnb.max())), flush=True)
+
+    def bench(rows, iters, what, tol=0.0):
         P = len(rows)
         gp, gT = gp_all[rows].contiguous(), gT_all[rows].contiguous()
         T = torch.empty(P, 12, dtype=torch.float64, device=d)
         fit, rm = (torch.empty(P, dtype=torch.float64, device=d) for _ in range(2))
         nc, it, st = (torch.empty(P, dtype=torch.int32, device=d) for _ in range(3))
 
+        tail = (fo.r, N.ptr(gp), N.ptr(gT), P, fo.r, iters, tol, tol, N.ptr(T), N.ptr(fit), N.ptr(rm), N.ptr(nc),
+                N.ptr(it), N.ptr(st), None, N.stream())
+
         def run():
-            assert L.mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M,
-                                    fo.r, N.ptr(gp), N.ptr(gT), P, fo.r, iters, 0.0, 0.0, N.ptr(T), N.ptr(fit),
-                                    N.ptr(rm), N.ptr(nc), N.ptr(it), N.ptr(st), None, N.stream()) == 0
+            if plane:
+                assert L.mvr_icp_refine_plane(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
+                                              N.ptr(fo.off_dev), fo.B, fo.M, *tail) == 0
+            else:
+                assert L.mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
+                                        fo.M, *tail) == 0
         ms = timed(run)
+        if tol > 0.0:
+            its = it.cpu().numpy()
+            print("%s %s, tolerances %g, cap %d: median %.3f ms (min %.3f, max %.3f); iterations min %d, median %d, "
+                  "mean %.1f, max %d; %d of %d at the cap; rmse mean %.4f"
+                  % (a.method, what, tol, iters, ms[len(ms) // 2], ms[0], ms[-1], its.min(), int(np.median(its)),
+                     its.mean(), its.max(), int((st.cpu().numpy() & 2 != 0).sum()), P, float(rm.mean())), flush=True)
+            return ms[len(ms) // 2]
         print("icp %s, %d iterations: median %.3f ms (min %.3f, max %.3f, %d calls); fitness %.3f..%.3f, rmse mean "
               "%.4f, status %s" % (what, iters, ms[len(ms) // 2], ms[0], ms[-1], a.reps, float(fit.min()),
                                    float(fit.max()), float(rm.mean()), sorted(set(st.tolist()))), flush=True)
@@ -85,6 +114,7 @@ def main():
     t1 = bench(every, 1, "%d pairs" % len(pairs))
     t30 = bench(every, 30, "%d pairs" % len(pairs))
     one = bench(every[:1], 30, "pair (0, 1) alone")
+    bench(every, 30, "%d pairs" % len(pairs), tol=1e-6)
     print("per evaluation: %.3f ms over the scene ((30 - 1 iterations) / 29), %.3f ms for the pair alone"
           % ((t30 - t1) / 29.0, one / 31.0), flush=True)
 
@@ -103,7 +133,7 @@ def main():
           "alone (0 iterations) %.3f ms" % (len(pairs), ms[len(ms) // 2], ms[0], ms[-1], t0), flush=True)
 
     host = []
-    for k in range(min(a.host_pairs, len(pairs))):
+    for k in range(0 if plane else min(a.host_pairs, len(pairs))):
         i, j = pairs[k]
         t = time.perf_counter()
         r = O.icp(cent[i], cent[j], T0[k], fo.r, 30, 0.0, 0.0)
