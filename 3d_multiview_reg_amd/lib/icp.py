@@ -100,6 +100,69 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     return out
 
 
+INFO_ORDERS = ("redwood", "open3d")
+_OPEN3D_PERM = (3, 4, 5, 0, 1, 2)
+
+
+def permute_information(info, order="open3d"):
+    """Swap the translation and rotation blocks of information matrices [..., 6, 6]: (v, omega) <-> (omega, v).  The
+    permutation is its own inverse; order 'redwood' returns the input."""
+    if order not in INFO_ORDERS:
+        raise ValueError("permute_information: order must be one of %s, not %r" % (", ".join(INFO_ORDERS), order))
+    if order == "redwood":
+        return info
+    p = list(_OPEN3D_PERM)
+    return info[..., p, :][..., :, p]
+
+
+def information_matrix(fo, pairs, T, max_dist=None, order="redwood"):
+    """The 6 x 6 information matrix of every pair at its transform, on the points of `fo` (csrc/info.hip
+    mvr_pair_information): sum G^T G over the correspondences eval(T) of icp_refine finds, G =
+    [I | -[y]x] at the matched target point y.  What Open3D's get_information_matrix_from_point_clouds(source,
+    target, max_dist, T) gives a pose-graph edge; Open3D parity is unpinned.
+
+    pairs [P,2] (source, target); T [P,4,4] or [P,3,4] with x_target ~ T x_source, numpy or torch, any float dtype;
+    max_dist at most fo.r (None: fo.r).  order 'redwood': parameters (translation, rotation), the order of a Redwood
+    .info file, of lib.utils.computeTransformationErr and of lib.multiview.optimize_pose_graph, info[:, 0, 0] ==
+    n_corr; 'open3d': (rotation, translation), Open3D's.
+    Returns a dict of fp64 info [P,6,6], int32 n_corr [P], fp64 rmse [P], int32 status [P] (0, or
+    STATUS_INVALID_PAIR with a zero matrix).  The outputs stay on the device when T was on the device; otherwise they
+    come back on the host (numpy for numpy inputs)."""
+    max_dist = float(fo.r if max_dist is None else max_dist)
+    if not max_dist > 0.0:
+        raise ValueError("information_matrix: max_dist must be positive")
+    if order not in INFO_ORDERS:
+        raise ValueError("information_matrix: order must be one of %s, not %r" % (", ".join(INFO_ORDERS), order))
+    if max_dist > fo.r:
+        raise ValueError("information_matrix: max_dist %g exceeds the index's cell size %g (build the "
+                         "FragmentOverlap with radius >= max_dist)" % (max_dist, fo.r))
+    was_numpy = not torch.is_tensor(T)
+    Tin = torch.as_tensor(T)
+    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("information_matrix: T must be a float [P,4,4] or [P,3,4]")
+    ij = torch.as_tensor(pairs)
+    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
+        raise ValueError("information_matrix: pairs must be [P,2] with one row per transform")
+    N.require_hip()
+    on_dev = Tin.device.type == "cuda"
+    dev = fo.device
+    P = int(Tin.shape[0])
+    T3 = Tin[:, :3, :].to(dev, torch.float64).contiguous()
+    ij = ij.to(dev, torch.int64).contiguous()
+    info = torch.empty(P, 36, dtype=torch.float64, device=dev)
+    rmse = torch.empty(P, dtype=torch.float64, device=dev)
+    n_corr, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(2))
+    N.check(N.lib().mvr_pair_information(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
+                                         fo.M, fo.r, N.ptr(ij), N.ptr(T3), P, max_dist, N.ptr(info), N.ptr(n_corr),
+                                         N.ptr(rmse), N.ptr(status), N.stream()), "mvr_pair_information")
+    out = {"info": permute_information(info.view(P, 6, 6), order), "n_corr": n_corr, "rmse": rmse, "status": status}
+    if not on_dev:
+        out = {k: v.cpu() for k, v in out.items()}
+        if was_numpy:
+            out = {k: v.numpy() for k, v in out.items()}
+    return out
+
+
 def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="point_to_point", normal_radius=None,
              **kw):
     """One pair in the shape of Open3D's registration_icp(source, target, max_correspondence_distance, init):

@@ -275,6 +275,24 @@ def read_trajectory_info(filename, dim=6):
     return n_frame, np.asarray(infos, dtype=np.float64).reshape(-1, dim, dim)
 
 
+def write_trajectory_info(info, metadata, filename, n_frames=None):
+    """The Redwood .info layout read_trajectory_info reads: per pair a line `i j n_frames` and the six rows of its
+    6 x 6 information matrix (parameter order translation, rotation; lib.icp.information_matrix).  The rows whose
+    metadata flag is True or 'True' are written, the rule of write_trajectory, so a scene's traj.txt and .info hold
+    the same pairs in the same order.  n_frames None: one more than the largest fragment index in the metadata, a lower
+    bound of the scene's fragment count, which the reference's files hold there (pass it where it is known)."""
+    info = np.asarray(info, dtype=np.float64).reshape(-1, 6, 6)
+    if n_frames is None:
+        n_frames = 1 + max([max(int(m[0]), int(m[1])) for m in metadata] + [-1])
+    with open(filename, "w") as f:
+        for i in range(info.shape[0]):
+            flag = metadata[i][2]
+            if flag is True or str(flag) == "True":
+                f.write("%d\t%d\t%d\n" % (int(metadata[i][0]), int(metadata[i][1]), int(n_frames)))
+                f.write("\n".join("\t".join("{0:.12f}".format(v) for v in row) for row in info[i].tolist()))
+                f.write("\n")
+
+
 def extract_corresponding_trajectors(est_pairs, gt_pairs, est_traj, gt_traj):
     """utils.py:534-560."""
     e = est_pairs[:, 0:2]

@@ -14,6 +14,9 @@ report), with the per-pair host loop replaced by batched GPU calls:
   * `--icp` (not in the reference): every estimate of a loader batch is first refined by point-to-point ICP on the
     points the overlap gate indexes (lib/icp.py, one call per batch); without the flag nothing changes.
     `--icp_method point_to_plane` minimises along normals estimated on those points over `--icp_normal_radius`.
+  * `--write_info` (not in the reference): the 6 x 6 information matrix of every pair at its estimate (lib/icp.py
+    information_matrix on the same points, one call per batch), written as `est.info` beside each scene's `traj.txt`
+    in the layout of gt.info; without the flag nothing changes.
 Optional reference dependencies that are absent here (open3d, coloredlogs, matplotlib) are not needed.
 A run without --model uses random-init weights (no checkpoint download offline) and says so.
 
@@ -35,13 +38,14 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from lib.utils import (ensure_dir, read_trajectory, write_trajectory, read_trajectory_info,  # noqa: E402
+                       write_trajectory_info,
                        get_folder_list, Timer, rotation_error, translation_error, load_config,
                        evaluate_registration, extract_corresponding_trajectors,
                        run_ransac_batch)
 from scripts.utils import make_pairwise_eval_data_loader  # noqa: E402
 from lib.checkpoints import CheckpointIO  # noqa: E402
 from lib.overlap import FragmentOverlap, _radius  # noqa: E402
-from lib.icp import icp_refine  # noqa: E402
+from lib.icp import icp_refine, information_matrix  # noqa: E402
 import lib.config as config  # noqa: E402
 
 SHORT_NAMES = {
@@ -85,16 +89,21 @@ def load_model(method, model_path, cfg_path=None):
 
 # per-pair record of the estimation loop: [pair idx, T_est (4 x 4, row-major), overlap flag, fragment i, fragment j]
 REC = 20
+REC_INFO = REC + 37   # --write_info: then the correspondence count and the 6 x 6 information matrix (row-major)
 
 
-def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overlap_threshold, icp=None):
+def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overlap_threshold, icp=None, info=None):
     """benchmark:193-224 for one loader batch: the estimate of every pair (batched: OANet + Procrustes, or RANSAC,
     on the GPU), T_est = inv(estimate), the overlap gate -> float64 records [b, REC].  `bi` is the batch's index
     in the whole evaluation (it seeds the RANSAC draws, so a batch gets the same draws on whichever rank it runs).
     icp = (max_dist, max_iters) (--icp): every estimate is first refined by point-to-point ICP on the points the
     overlap gate indexes (lib.icp.icp_refine, one call per batch); the gate and the record use the refined one.
     icp = (max_dist, max_iters, 'point_to_plane', normal_radius): by point-to-plane ICP, on normals estimated on
-    those points over normal_radius."""
+    those points over normal_radius.
+    info = max_dist (--write_info): the records are REC_INFO wide and carry every pair's information matrix at the
+    estimate whose inverse is written (the refined one under --icp), on the same points (lib.icp.information_matrix,
+    one call per batch): parameters (translation, rotation) about the origin of fragment j's frame, the frame in which
+    evaluate_registration's error motion inv(gt) est acts."""
     xs = batch["xs"][:, 0].numpy()
     if method == "RANSAC":
         T = _ransac(xs, seed=seed + bi)
@@ -118,15 +127,18 @@ def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overl
             fo.estimate_normals(icp[3])
         T = icp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1],
                        **({"method": icp[2]} if len(icp) > 2 else {}))["T"]
+    im = information_matrix(fo, pairs, T, max_dist=info) if info is not None and b else None
     T_est = np.linalg.inv(T)
     ratios = fo.ratios(pairs, list(T_est)) if b else []
-    rec = np.zeros((b, REC), np.float64)
+    rec = np.zeros((b, REC if info is None else REC_INFO), np.float64)
     for k in range(b):
         meta = batch["metadata"][k]
         rec[k, 0] = int(batch["idx"][k].numpy().item())
         rec[k, 1:17] = T_est[k].reshape(16)
         rec[k, 17] = float(ratios[k] >= overlap_threshold)
         rec[k, 18], rec[k, 19] = int(meta[1]), int(meta[2])
+        if im is not None:
+            rec[k, 20], rec[k, 21:57] = im["n_corr"][k], im["info"][k].reshape(36)
     return rec
 
 
@@ -142,8 +154,9 @@ def _gather_records(rec, num_pairs, batch_size, world, pg=None):
 
 
 def estimate_trans_params(eval_data, source_path, dataset, scene_info, method, model, mutuals,
-                          overlap_method="FCGF", refine=False, seed=0, world=1, rank=0, icp=None):
-    """benchmark:56-133 (method RANSAC) and :137-245 (learned filters), batched: writes traj.txt per scene.
+                          overlap_method="FCGF", refine=False, seed=0, world=1, rank=0, icp=None, info=None):
+    """benchmark:56-133 (method RANSAC) and :137-245 (learned filters), batched: writes traj.txt per scene (and with
+    info = max_dist, est.info beside it: the same pairs in the same order).
     world > 1: `eval_data` is this rank's block of whole loader batches (lib.data.make_pairwise_eval_data_loader);
     the per-pair records are all-gathered and rank 0 writes the trajectories."""
     num_pairs = scene_info["nr_examples"]
@@ -162,9 +175,10 @@ def estimate_trans_params(eval_data, source_path, dataset, scene_info, method, m
         # the ICP settings travel as a keyword, and only when asked for: the positional signature is what stand-ins
         # of _batch_records implement
         recs.append(_batch_records(batch, first // bsz + bi, method, model, refine, seed, overlap_method,
-                                   overlap_threshold, **({} if icp is None else {"icp": icp})))
+                                   overlap_threshold, **({} if icp is None else {"icp": icp}),
+                                   **({} if info is None else {"info": info})))
         timer.toc()
-    rec = np.concatenate(recs) if recs else np.zeros((0, REC), np.float64)
+    rec = np.concatenate(recs) if recs else np.zeros((0, REC if info is None else REC_INFO), np.float64)
     rec = _gather_records(rec, num_pairs, bsz, world)
     if num_pairs and recs:
         logging.info("%d pairwise registration parameters estimated in %.3fs (%.4fs per batch of pure run time)",
@@ -186,14 +200,18 @@ def estimate_trans_params(eval_data, source_path, dataset, scene_info, method, m
         ensure_dir(os.path.join(save_path, key))
         write_trajectory(est[rng[0]:rng[1], :].reshape(-1, 4, 4), reg_metadata[rng[0] // 4:rng[1] // 4],
                          os.path.join(save_path, key, "traj.txt"))
+        if info is not None:
+            write_trajectory_info(rec[rng[0] // 4:rng[1] // 4, 21:57], reg_metadata[rng[0] // 4:rng[1] // 4],
+                                  os.path.join(save_path, key, "est.info"))
 
 
 def evaluate_registration_performance(eval_data, source_path, dataset, scene_info, method, model, mutuals=False,
-                                      overlap_method="FCGF", refine=False, seed=0, world=1, rank=0, icp=None):
+                                      overlap_method="FCGF", refine=False, seed=0, world=1, rank=0, icp=None,
+                                      info=None):
     """benchmark:250-345: estimate (scenes without results), then the per-scene report; returns the summary.
     world > 1: rank 0 writes the trajectories and the report; every rank returns rank 0's summary."""
     estimate_trans_params(eval_data, source_path, dataset, scene_info, method, model, mutuals, overlap_method,
-                          refine, seed, world, rank, icp)
+                          refine, seed, world, rank, icp, info)
     if world > 1:
         import torch.distributed as dist
         box = [_report(source_path, dataset, method, mutuals) if rank == 0 else None]
@@ -263,6 +281,10 @@ def parser():
                     help="what --icp minimises: point distances, or distances along the target's normals")
     ap.add_argument("--icp_normal_radius", type=float, default=None, help="point_to_plane: the radius of the normal "
                     "estimation, at most the overlap gate's radius for --overlap_method, which is the default")
+    ap.add_argument("--write_info", action="store_true", help="write every pair's 6 x 6 information matrix at its "
+                    "estimate as est.info beside each scene's traj.txt (the layout of gt.info)")
+    ap.add_argument("--info_max_dist", type=float, default=None, help="--write_info: the correspondence distance, at "
+                    "most the overlap gate's radius for --overlap_method, which is the default")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--dist_backend", default=None, choices=["nccl", "gloo"],
                     help="under torchrun (WORLD_SIZE > 1): the process group's backend (default nccl = RCCL on a GPU "
@@ -293,10 +315,17 @@ def main(argv=None):
             if not 0.0 < icp[3] <= radius:
                 raise ValueError("--icp_normal_radius must lie in (0, %g] for --overlap_method %s"
                                  % (radius, args.overlap_method))
+    info = None
+    if args.write_info:
+        radius = _radius(args.overlap_method, 0.025)
+        info = radius if args.info_max_dist is None else args.info_max_dist
+        if not 0.0 < info <= radius:
+            raise ValueError("--info_max_dist must lie in (0, %g] for --overlap_method %s"
+                             % (radius, args.overlap_method))
     with torch.no_grad():
         return evaluate_registration_performance(eval_data, args.source_path, args.dataset, scene_info, args.method,
                                                  model, args.mutuals, args.overlap_method, args.refine, args.seed,
-                                                 world, rank, icp)
+                                                 world, rank, icp, **({} if info is None else {"info": info}))
 
 
 if __name__ == "__main__":

@@ -393,6 +393,80 @@ int mvr_icp_refine_plane(const void* index, size_t index_bytes, const double* xy
                          double* fitness, double* rmse, int32_t* n_corr, int32_t* iters, int32_t* status,
                          double* trace, mvr_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Per-pair 6 x 6 information matrices on a radius index (csrc/info.hip): what Open3D's
+ * get_information_matrix_from_point_clouds gives a pose-graph edge, restated from the maths.
+ * The arguments are those of mvr_icp_refine without the loop settings; T [P,12] (3x4 row-major) is evaluated as it
+ * is.  The correspondences of pair p are exactly those of eval(T) of mvr_icp_refine: the target point y nearest to
+ * q = R x + t, valid iff sqrt(ex*ex + ey*ey + ez*ez) < max_dist (strict), the lowest row on equal distances.
+ *   info [P,36] row-major = sum over the valid correspondences of G_y^T G_y with G_y = [ I3 | -[y]x ] (3 x 6), y the
+ *   target point: the parameter order is (translation v, rotation omega), the order lib.utils
+ *   computeTransformationErr assumes, so info[0] == n_corr exactly, and xi^T info xi is the summed squared
+ *   displacement of the matched target-side points under the small motion q -> q + v + omega x q about the target
+ *   frame's origin.  Open3D uses the same G with the blocks in (omega, v) order (lib.icp.information_matrix offers
+ *   that permutation).  Open3D is absent here, so Open3D parity is unpinned; Redwood's published .info files are
+ *   not pinned either: whether they were built with omega or with the quaternion's vector part (a factor of 2 on the
+ *   rotation block) cannot be checked here.
+ *   n_corr [P] (may be NULL), rmse [P] = sqrt(sum d^2 / n_corr) (0 without correspondences), status [P]: 0, or 4 for
+ *   an invalid pair by the rules of mvr_icp_refine's bit 4 — then info all zero, n_corr = 0, rmse = 0.
+ *   fp64 throughout; one workgroup per pair, no atomics, no workspace, the reduction in a fixed order: a pair's
+ *   outputs are a function of the pair alone (bit-identical whatever the batch around it).
+ *   MVR_EINVAL, scalars first: negative P or M; B <= 0 or B >= 32768; M >= 2^31; max_dist or r_index <= 0;
+ *   max_dist > r_index.  P == 0 then returns MVR_OK.  With P > 0: a NULL pairs, T, info, rmse or status; with M > 0
+ *   a NULL index, xyz or off, or index_bytes < mvr_radius_index_bytes(M).
+ * ---------------------------------------------------------------------- */
+int mvr_pair_information(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
+                         int64_t M, double r_index, const int64_t* pairs, const double* T, int P, double max_dist,
+                         double* info, int32_t* n_corr, double* rmse, int32_t* status, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Pose-graph refinement over SE(3), batched over scenes (csrc/posegraph.hip): the Levenberg-
+ * Marquardt stage of Open3D's global_optimization / Choi et al. 2015, restated from the maths (Open3D parity is
+ * unpinned; no line process or robust kernel).  tests/posegraph_oracle.py is the normative text.
+ *   Scenes, edges, fragments, strides and conventions are mvr_sync_poses': edge e = (i, j) with x_j ~ T_e x_i,
+ *   T_e = (R_pair, t_pair); pose M_f: X = R_f x_f + t_f.  info [., 36]: the edge's 6 x 6 matrix in (v, omega) order
+ *   (mvr_pair_information's), rows as R_pair; (info + info^T) / 2 is what is used.  R0 [., 9], t0 [., 3]: the initial
+ *   poses, rows as R / t.  The anchor's pose is held at its input value.
+ *   Residual: D_e = M_j^-1 M_i T_e^-1, xi_e = (v, omega) with v the translation of D_e and omega the rotation vector
+ *   of its rotation: a = vee(D - D^T) / 2, theta = atan2(|a|, (tr D - 1) / 2), omega = a theta / |a| (|a| <= 1e-8:
+ *   a (1 + theta^2 / 6); inaccurate near theta = pi, where no edge of a sane start lies).
+ *   Cost c = sum_e w_e xi_e^T info_e xi_e.  Update delta_f = (dv, dw), applied on the left: R_f <- Exp(dw) R_f,
+ *   t_f <- Exp(dw) t_f + dv.  First-order Jacobian: d xi_e / d delta_i = A_e, d xi_e / d delta_j = -A_e,
+ *   A_e = Ad(M_j^-1) = [[R_j^T, -R_j^T [t_j]x], [0, R_j^T]].  H = sum w J^T info J, g = sum w J^T info xi; the rows
+ *   and columns of the anchor and of the non-members are replaced by identity.
+ *   Members: the fragments reachable from the anchor over edges with w > 0; an edge with a non-member end gets
+ *   weight 0; non-members come out with their input pose and member 0.
+ *   Loop: lambda = lambda0.  A trial solves (H + lambda diag H) delta = -g by Cholesky, forms the candidate poses and
+ *   their cost c'; c' < c accepts (lambda /= 10), otherwise the poses stay (lambda *= 10).  A pivot that is not
+ *   positive is a rejected trial without a candidate.  Every trial counts in iters.  Converged: after an accepted
+ *   trial with c - c' <= tol_cost c, after any trial that had a candidate with max|delta| <= tol_step (applied if it
+ *   was accepted), or when c == 0 (also at the start).  Both tolerances 0: max_iters trials unless c reaches 0 or
+ *   delta is exactly 0.
+ *   Outputs: R, t, member (may be NULL), cost [S,2] (initial, final), iters [S], status [S], trace [S, max_iters + 1]
+ *   (may be NULL): the cost held at the start and after every trial (unchanged by a rejected one), -1 after the last.
+ *   Status bits: 1 some fragment is not a member; 2 max_iters trials without convergence while a tolerance is
+ *   positive; 4 an edge was ignored (index out of range, i == j, a non-finite T, info or w, a negative w, or
+ *   max|info - info^T| > 1e-9 |info|_F), or the scene is invalid (anchor >= n_frags[s], a count negative or above its
+ *   maximum, n_frags 0 with edges, a non-finite initial pose): the poses are copied through, member 0, cost 0,
+ *   iters 0, bit 1 as well when it has fragments; 8 the last trial's factorisation failed.
+ *   fp64 throughout; one workgroup per scene, every trial inside the one launch, no floating-point or global
+ *   atomics (two flag words in LDS are set by an idempotent atomicOr): a scene's outputs are a function of the
+ *   scene alone.  max_frags <= MVR_SYNC_MAX_FRAGS; workspace (8-byte aligned) >=
+ *   mvr_posegraph_workspace_bytes(S, max_frags, max_edges).
+ *   MVR_EINVAL: negative S / max_frags / max_edges / max_iters; max_frags above the maximum; anchor outside
+ *   [0, max_frags) (when max_frags > 0); lambda0 negative or non-finite; a negative tolerance.  S == 0 or
+ *   max_frags == 0 then returns MVR_OK.  Otherwise a NULL n_edges, n_frags, R0, t0, R, t, cost, iters or status; with
+ *   max_edges > 0 a NULL R_pair, t_pair, ij or info; a short or misaligned workspace; with S > 1 a stride below its
+ *   maximum count.
+ * ---------------------------------------------------------------------- */
+size_t mvr_posegraph_workspace_bytes(int S, int max_frags, int max_edges);
+int mvr_posegraph_optimize(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w,
+                           const double* info, int64_t e_sstride, const int32_t* n_edges, const int32_t* n_frags,
+                           int S, int max_frags, int max_edges, int anchor, const double* R0, const double* t0,
+                           int max_iters, double lambda0, double tol_cost, double tol_step, double* R, double* t,
+                           int64_t f_sstride, int32_t* member, double* cost, int32_t* iters, int32_t* status,
+                           double* trace, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
+
 /* Farthest point sampling per fragment (Sampler 'fps', lib/layers.py:134-141 — pointnet2
  * furthest_point_sample semantics of oracle/fps.py: seed = first point, running min of squared
  * distances, first maximum on ties).  xyz [sum n][3] with fragment row offsets (device `offsets`
