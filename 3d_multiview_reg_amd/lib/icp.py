@@ -1,11 +1,13 @@
 """Fine registration: batched ICP on the fragments' own points, point-to-point (csrc/icp.hip mvr_icp_refine,
-DESIGN.md 4.19) or point-to-plane on normals (csrc/icp_plane.hip mvr_icp_refine_plane); the semantics
-are in include/mvreg.h.
+DESIGN.md 4.19), point-to-plane on normals (csrc/icp_plane.hip mvr_icp_refine_plane) or generalized,
+plane-to-plane, on both fragments' normals (csrc/icp_gicp.hip mvr_icp_refine_generalized); the
+semantics are in include/mvreg.h.
 
 The reference stops at the coarse estimate (Procrustes or RANSAC over the sampled correspondences); its users
 follow it with Open3D's `registration_icp`.  `icp_refine` does that for every pair of a scene in one launch, on the
-radius index a `FragmentOverlap` already holds; `icp_pair` keeps the one-pair shape of `registration_icp`.  Restated
-from the maths and pinned to tests/icp_oracle.py: Open3D parity is unpinned.
+radius index a `FragmentOverlap` already holds; `icp_pair` keeps the one-pair shape of `registration_icp`.
+`gicp_refine` and `gicp_pair` are the same two shapes for `registration_generalized_icp`.  Restated from the maths
+and pinned to tests/icp_oracle.py, tests/icp_plane_oracle.py and tests/gicp_oracle.py: Open3D parity is unpinned.
 
 Convention: T maps source coordinates into the target's frame, x_target ~ R x_source + t (rot_est / trans_est of
 filter_correspondences, the input of lib.multiview.synchronize) — the inverse of the `trans` of
@@ -16,7 +18,7 @@ import torch
 from lib import _native as N
 
 STATUS_FEW_CORRESPONDENCES, STATUS_ITERATION_CAP, STATUS_INVALID_PAIR = 1, 2, 4
-STATUS_DEGENERATE = 8     # point-to-plane only: the 6 x 6 system is not positive definite to working precision
+STATUS_DEGENERATE = 8     # not point-to-point: the 6 x 6 system is not positive definite to working precision
 METHODS = ("point_to_point", "point_to_plane")
 
 
@@ -197,4 +199,97 @@ def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="p
         fo.estimate_normals(nr)
     T0 = T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None]
     out = icp_refine(fo, [[0, 1]], T0, max_dist, method=method, **kw)
+    return {k: v[0] for k, v in out.items()}
+
+
+def _check_epsilon(name, epsilon):
+    if not 0.0 < epsilon <= 1.0:
+        raise ValueError("%s: epsilon must lie in (0, 1]" % name)
+
+
+def gicp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, epsilon=1e-3,
+                return_trace=False):
+    """Generalized (plane-to-plane) ICP on every pair of `fo`: icp_refine's arguments, conventions, stopping rule and
+    dict, with the solve of Segal et al.'s GICP (Open3D's registration_generalized_icp; parity unpinned).
+
+    Every point's covariance is 1 in its surface and `epsilon` along its normal, so both fragments' surfaces weigh a
+    residual.  fo.normals (fp64 [M,3] on the device, from fo.estimate_normals() or assigned by the caller) must be
+    there and unit: they are not renormalised, their sign does not matter.  epsilon in (0, 1]; 1 makes the normals
+    drop out.  status bit STATUS_DEGENERATE as for 'point_to_plane'."""
+    max_dist = float(fo.r if max_dist is None else max_dist)
+    _check_settings("gicp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
+    _check_epsilon("gicp_refine", epsilon)
+    if max_dist > fo.r:
+        raise ValueError("gicp_refine: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
+                         "radius >= max_dist)" % (max_dist, fo.r))
+    was_numpy = not torch.is_tensor(T_init)
+    Tin = torch.as_tensor(T_init)
+    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("gicp_refine: T_init must be a float [P,4,4] or [P,3,4]")
+    ij = torch.as_tensor(pairs)
+    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
+        raise ValueError("gicp_refine: pairs must be [P,2] with one row per transform")
+    nrm = getattr(fo, "normals", None)
+    if nrm is None:
+        raise ValueError("gicp_refine: needs fo.normals (call fo.estimate_normals())")
+    if not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64 or \
+            nrm.device != fo.xyz.device or not nrm.is_contiguous():
+        raise ValueError("gicp_refine: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
+                         % fo.M)
+    N.require_hip()
+    on_dev = Tin.device.type == "cuda"
+    dev = fo.device
+    P, rows = int(Tin.shape[0]), int(max_iters) + 1
+    T0 = Tin[:, :3, :].to(dev, torch.float64).contiguous()
+    ij = ij.to(dev, torch.int64).contiguous()
+    T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
+    fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
+    n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    trace = torch.empty(P, rows, 2, dtype=torch.float64, device=dev) if return_trace else None
+    N.check(N.lib().mvr_icp_refine_generalized(
+        N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals), N.ptr(fo.off_dev), fo.B, fo.M, fo.r,
+        N.ptr(ij), N.ptr(T0), P, max_dist, float(epsilon), int(max_iters), float(tol_fitness), float(tol_rmse),
+        N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream()),
+        "mvr_icp_refine_generalized")
+    T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
+    T4[:, :3], T4[:, 3, 3] = T, 1.0
+    out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
+    if return_trace:
+        out["trace"] = trace
+    if not on_dev:
+        out = {k: v.cpu() for k, v in out.items()}
+        if was_numpy:
+            out = {k: v.numpy() for k, v in out.items()}
+    return out
+
+
+def gicp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, normal_radius=None, epsilon=1e-3, **kw):
+    """One pair in the shape of Open3D's registration_generalized_icp(source, target, max_correspondence_distance,
+    init): icp_pair's arguments.  The normals of both clouds are estimated here over normal_radius (None: max_dist) on
+    an index of cell max(max_dist, normal_radius).  **kw: max_iters, tol_fitness, tol_rmse, return_trace of
+    gicp_refine.  Returns gicp_refine's dict without the leading [P]."""
+    from lib.overlap import FragmentOverlap
+    _check_settings("gicp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
+                    kw.get("tol_rmse", 0.0))
+    _check_epsilon("gicp_pair", epsilon)
+    if normal_radius is not None and not normal_radius > 0.0:
+        raise ValueError("gicp_pair: normal_radius must be positive")
+    if voxel_size is not None and not voxel_size > 0.0:
+        raise ValueError("gicp_pair: voxel_size must be positive")
+    for name, x in (("src_xyz", src_xyz), ("tgt_xyz", tgt_xyz)):
+        shape = tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("gicp_pair: %s must be [n,3]" % name)
+    Tin = torch.as_tensor(T_init)
+    if tuple(Tin.shape) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("gicp_pair: T_init must be a float [4,4] or [3,4]")
+    nr = max_dist if normal_radius is None else normal_radius
+    cell = max(max_dist, nr)                             # the index's cells cover the search ball and the normals'
+    if voxel_size is None:
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell)
+    else:
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell)
+    fo.estimate_normals(nr)
+    T0 = T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None]
+    out = gicp_refine(fo, [[0, 1]], T0, max_dist, epsilon=epsilon, **kw)
     return {k: v[0] for k, v in out.items()}

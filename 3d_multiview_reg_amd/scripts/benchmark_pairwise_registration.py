@@ -13,7 +13,8 @@ report), with the per-pair host loop replaced by batched GPU calls:
     errors per scene against gt.log / gt.info (benchmark:250-345);
   * `--icp` (not in the reference): every estimate of a loader batch is first refined by point-to-point ICP on the
     points the overlap gate indexes (lib/icp.py, one call per batch); without the flag nothing changes.
-    `--icp_method point_to_plane` minimises along normals estimated on those points over `--icp_normal_radius`.
+    `--icp_method point_to_plane` minimises along normals estimated on those points over `--icp_normal_radius`;
+    `--icp_method generalized` is plane-to-plane ICP on the same normals, of both fragments (`--icp_gicp_epsilon`).
   * `--write_info` (not in the reference): the 6 x 6 information matrix of every pair at its estimate (lib/icp.py
     information_matrix on the same points, one call per batch), written as `est.info` beside each scene's `traj.txt`
     in the layout of gt.info; without the flag nothing changes.
@@ -45,7 +46,7 @@ from lib.utils import (ensure_dir, read_trajectory, write_trajectory, read_traje
 from scripts.utils import make_pairwise_eval_data_loader  # noqa: E402
 from lib.checkpoints import CheckpointIO  # noqa: E402
 from lib.overlap import FragmentOverlap, _radius  # noqa: E402
-from lib.icp import icp_refine, information_matrix  # noqa: E402
+from lib.icp import gicp_refine, icp_refine, information_matrix  # noqa: E402
 import lib.config as config  # noqa: E402
 
 SHORT_NAMES = {
@@ -99,7 +100,8 @@ def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overl
     icp = (max_dist, max_iters) (--icp): every estimate is first refined by point-to-point ICP on the points the
     overlap gate indexes (lib.icp.icp_refine, one call per batch); the gate and the record use the refined one.
     icp = (max_dist, max_iters, 'point_to_plane', normal_radius): by point-to-plane ICP, on normals estimated on
-    those points over normal_radius.
+    those points over normal_radius.  icp = (max_dist, max_iters, 'generalized', normal_radius, epsilon): by
+    generalized ICP (lib.icp.gicp_refine) on the same normals.
     info = max_dist (--write_info): the records are REC_INFO wide and carry every pair's information matrix at the
     estimate whose inverse is written (the refined one under --icp), on the same points (lib.icp.information_matrix,
     one call per batch): parameters (translation, rotation) about the origin of fragment j's frame, the frame in which
@@ -125,8 +127,11 @@ def _batch_records(batch, bi, method, model, refine, seed, overlap_method, overl
     if icp is not None and b:
         if len(icp) > 2:
             fo.estimate_normals(icp[3])
-        T = icp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1],
-                       **({"method": icp[2]} if len(icp) > 2 else {}))["T"]
+        if len(icp) > 2 and icp[2] == "generalized":
+            T = gicp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1], epsilon=icp[4])["T"]
+        else:
+            T = icp_refine(fo, pairs, T, max_dist=icp[0], max_iters=icp[1],
+                           **({"method": icp[2]} if len(icp) > 2 else {}))["T"]
     im = information_matrix(fo, pairs, T, max_dist=info) if info is not None and b else None
     T_est = np.linalg.inv(T)
     ratios = fo.ratios(pairs, list(T_est)) if b else []
@@ -277,10 +282,15 @@ def parser():
     ap.add_argument("--icp_max_dist", type=float, default=None, help="ICP correspondence distance, at most the "
                     "overlap gate's radius for --overlap_method, which is the default")
     ap.add_argument("--icp_iters", type=int, default=30, help="ICP iteration cap")
-    ap.add_argument("--icp_method", default="point_to_point", choices=["point_to_point", "point_to_plane"],
-                    help="what --icp minimises: point distances, or distances along the target's normals")
-    ap.add_argument("--icp_normal_radius", type=float, default=None, help="point_to_plane: the radius of the normal "
-                    "estimation, at most the overlap gate's radius for --overlap_method, which is the default")
+    ap.add_argument("--icp_method", default="point_to_point",
+                    choices=["point_to_point", "point_to_plane", "generalized"],
+                    help="what --icp minimises: point distances, distances along the target's normals, or distances "
+                    "weighted by both fragments' surfaces (generalized, plane-to-plane ICP)")
+    ap.add_argument("--icp_normal_radius", type=float, default=None, help="point_to_plane and generalized: the radius "
+                    "of the normal estimation, at most the overlap gate's radius for --overlap_method, which is the "
+                    "default")
+    ap.add_argument("--icp_gicp_epsilon", type=float, default=1e-3, help="generalized: a point's covariance along its "
+                    "normal (1 in the surface), in (0, 1]")
     ap.add_argument("--write_info", action="store_true", help="write every pair's 6 x 6 information matrix at its "
                     "estimate as est.info beside each scene's traj.txt (the layout of gt.info)")
     ap.add_argument("--info_max_dist", type=float, default=None, help="--write_info: the correspondence distance, at "
@@ -310,11 +320,15 @@ def main(argv=None):
         if not 0.0 < icp[0] <= radius or icp[1] < 0:
             raise ValueError("--icp_max_dist must lie in (0, %g] for --overlap_method %s, --icp_iters must not be "
                              "negative" % (radius, args.overlap_method))
-        if args.icp_method == "point_to_plane":   # the default method keeps the two settings it always had
-            icp += ("point_to_plane", radius if args.icp_normal_radius is None else args.icp_normal_radius)
+        if args.icp_method != "point_to_point":   # the default method keeps the two settings it always had
+            icp += (args.icp_method, radius if args.icp_normal_radius is None else args.icp_normal_radius)
             if not 0.0 < icp[3] <= radius:
                 raise ValueError("--icp_normal_radius must lie in (0, %g] for --overlap_method %s"
                                  % (radius, args.overlap_method))
+        if args.icp_method == "generalized":
+            icp += (args.icp_gicp_epsilon,)
+            if not 0.0 < icp[4] <= 1.0:
+                raise ValueError("--icp_gicp_epsilon must lie in (0, 1]")
     info = None
     if args.write_info:
         radius = _radius(args.overlap_method, 0.025)

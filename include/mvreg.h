@@ -291,8 +291,8 @@ int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_
                         size_t workspace_bytes, double* out_xyz, int64_t* out_off, mvr_stream_t stream);
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
- * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals and mvr_icp_refine_plane calls on the same
- * points.  B < 32768.
+ * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane and
+ * mvr_icp_refine_generalized calls on the same points.  B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
  * cells of a fragment form one run of the sorted order under one hash entry, a query walks the whole run, and
@@ -392,6 +392,41 @@ int mvr_icp_refine_plane(const void* index, size_t index_bytes, const double* xy
                          int P, double max_dist, int max_iters, double tol_fitness, double tol_rmse, double* T,
                          double* fitness, double* rmse, int32_t* n_corr, int32_t* iters, int32_t* status,
                          double* trace, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Generalized (plane-to-plane) ICP refinement, batched over pairs (csrc/icp_gicp.hip): the loop of
+ * Segal et al.'s GICP, Open3D's registration_generalized_icp, restated from the maths; Open3D parity is unpinned.
+ * The arguments are those of mvr_icp_refine_plane plus epsilon.  normals [M,3] (the row order of xyz) covers every
+ * fragment: a pair uses the normals of its source and of its target.  They are taken as given and NOT renormalised:
+ * they must be unit (mvr_estimate_normals output is unit to 1e-14).  Their sign does not matter: only n n^T enters.
+ *   A point with unit normal n has covariance C = I - (1 - epsilon) n n^T: 1 in the surface, epsilon along the
+ *   normal (what Open3D's GICP assigns, from given normals or from the neighbourhood covariance).
+ *   eval(T), fitness, rmse, n_corr: exactly mvr_icp_refine's (Euclidean distances), so the three methods' figures
+ *   compare.
+ *   Loop: state = eval(T0); up to max_iters times: stop with status bit 1 when n_corr < 6.  Over the valid pairs
+ *   q = T x, y its match, R the rotation part of T, n the normal of y, m = R n_s with n_s the normal of x, c = the
+ *   target fragment's first point (the per-pair origin of mvr_icp_refine_plane):
+ *     M = 2 I - (1 - epsilon)(n n^T + m m^T)   (= C_y + R C_x R^T for unit normals and orthonormal R)
+ *     A = M^-1, symmetric 3 x 3, inverted in closed form (cofactors over the determinant); eigenvalues of M in
+ *     [2 epsilon, 2]
+ *     G = [ -[q - c]x | I ]  (3 x 6: rotation first, translation last, as in mvr_icp_refine_plane),  d = q - y
+ *     H = sum G^T A G,  g = sum G^T A d;  solve H xi = -g by Cholesky.
+ *   A pivot that fails pivot > 1e-12 max_i H_ii (a NaN fails it too) stops the loop with status bit 8, T kept, iters
+ *   not counted; normals that make M singular or non-finite end there.  Otherwise D = [R_inc | xi[3:6] + c - R_inc c],
+ *   R_inc = Rz(xi[2]) Ry(xi[1]) Rx(xi[0]), and T <- D T: increments compose and T is not re-orthonormalised.
+ *   new = eval(T); the stopping rule, bit 2, bit 4, the trace, the NULL outputs and the invalid-pair behaviour are
+ *   mvr_icp_refine's.  epsilon == 1: M = 2 I, the normals drop out, and the loop is Gauss-Newton point-to-point.
+ *   Status bits: 1 fewer than 6 correspondences; 2 the cap; 4 an invalid pair; 8 a degenerate system.
+ *   fp64 throughout; one workgroup per pair, every iteration inside the one launch, no atomics, no workspace; a
+ *   pair's outputs are a function of the pair alone.
+ *   MVR_EINVAL: the rules of mvr_icp_refine_plane; also epsilon outside (0, 1] (a NaN included), checked with the
+ *   scalars before P == 0 returns MVR_OK.
+ * ---------------------------------------------------------------------- */
+int mvr_icp_refine_generalized(const void* index, size_t index_bytes, const double* xyz, const double* normals,
+                               const int64_t* off, int B, int64_t M, double r_index, const int64_t* pairs,
+                               const double* T0, int P, double max_dist, double epsilon, int max_iters,
+                               double tol_fitness, double tol_rmse, double* T, double* fitness, double* rmse,
+                               int32_t* n_corr, int32_t* iters, int32_t* status, double* trace, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Per-pair 6 x 6 information matrices on a radius index (csrc/info.hip): what Open3D's

@@ -1,15 +1,18 @@
-"""Timing of the ICP refinement (csrc/icp.hip mvr_icp_refine, or with --method point_to_plane csrc/icp_plane.hip
-mvr_icp_refine_plane after csrc/normals.hip mvr_estimate_normals) at the benchmark's scene shape: the 30-fragment synthetic
+"""Timing of the ICP refinement (csrc/icp.hip mvr_icp_refine, with --method point_to_plane csrc/icp_plane.hip
+mvr_icp_refine_plane or with --method generalized csrc/icp_gicp.hip mvr_icp_refine_generalized, both after
+csrc/normals.hip mvr_estimate_normals) at the benchmark's scene shape: the 30-fragment synthetic
 scene's 435 pairs on its 0.025 m voxel centroids, ground-truth starts perturbed by 2 degrees / sigma 2 cm, max_dist =
 the index's cell (0.075 m), both tolerances 0 — 1 and 30 iterations, one pair alone, and for scale the scene's
 mvr_radius_overlap_count call on the same index (one 27-cell walk with early exit per query, both directions) and
 the host oracle (tests/icp_oracle.py: sklearn kd-tree + numpy SVD) on the first --host_pairs pairs.  HIP events around
-each call after a warm-up, median over --reps calls.  point_to_plane also times the normal estimation (radius = the
-cell), and both methods report the iterations to convergence at tolerances 1e-6 from the same starts.
+each call after a warm-up, median over --reps calls.  point_to_plane and generalized also time the normal estimation
+(radius = the cell; generalized takes --epsilon), and every method reports the iterations to convergence at
+tolerances 1e-6 from the same starts.
 A library built with another workgroup size (tools/build_variant.sh icp.hip icp512 -DMVR_ICP_THREADS=512, or
-icp_plane.hip plane512 -DMVR_ICP_PLANE_THREADS=512, normals.hip nrm256 -DMVR_NORMALS_THREADS=256;
-MVR_LIB=tools/vsp/icp512.so) times that variant.
-usage: python tools/icp_micro.py [--method point_to_point|point_to_plane] [--frags 30] [--reps 7] [--host_pairs 4]"""
+icp_plane.hip plane512 -DMVR_ICP_PLANE_THREADS=512, icp_gicp.hip gicp512 -DMVR_ICP_GICP_THREADS=512, normals.hip
+nrm256 -DMVR_NORMALS_THREADS=256; MVR_LIB=tools/vsp/icp512.so) times that variant.
+usage: python tools/icp_micro.py [--method point_to_point|point_to_plane|generalized] [--epsilon 1e-3] [--frags 30]
+                                 [--reps 7] [--host_pairs 4]"""
 import argparse
 import os
 import sys
@@ -32,7 +35,8 @@ def main():
     ap.add_argument("--frags", type=int, default=30)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--host_pairs", type=int, default=4)
-    ap.add_argument("--method", default="point_to_point", choices=["point_to_point", "point_to_plane"])
+    ap.add_argument("--method", default="point_to_point", choices=["point_to_point", "point_to_plane", "generalized"])
+    ap.add_argument("--epsilon", type=float, default=1e-3)
     a = ap.parse_args()
     d = torch.device("cuda")
     frags, poses = synth_scene_fragments(n_frag=a.frags)
@@ -67,8 +71,8 @@ def main():
         ms.sort()
         return ms
 
-    plane = a.method == "point_to_plane"
-    if plane:
+    plane, gicp = a.method == "point_to_plane", a.method == "generalized"
+    if plane or gicp:
         nrm = torch.empty(fo.M, 3, dtype=torch.float64, device=d)
         nnb = torch.empty(fo.M, dtype=torch.int32, device=d)
 
@@ -90,7 +94,11 @@ def main():
                 N.ptr(it), N.ptr(st), None, N.stream())
 
         def run():
-            if plane:
+            if gicp:
+                assert L.mvr_icp_refine_generalized(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
+                                                    N.ptr(fo.off_dev), fo.B, fo.M, *tail[:5], a.epsilon,
+                                                    *tail[5:]) == 0
+            elif plane:
                 assert L.mvr_icp_refine_plane(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
                                               N.ptr(fo.off_dev), fo.B, fo.M, *tail) == 0
             else:
@@ -133,7 +141,7 @@ def main():
           "alone (0 iterations) %.3f ms" % (len(pairs), ms[len(ms) // 2], ms[0], ms[-1], t0), flush=True)
 
     host = []
-    for k in range(0 if plane else min(a.host_pairs, len(pairs))):
+    for k in range(0 if plane or gicp else min(a.host_pairs, len(pairs))):
         i, j = pairs[k]
         t = time.perf_counter()
         r = O.icp(cent[i], cent[j], T0[k], fo.r, 30, 0.0, 0.0)
