@@ -114,6 +114,10 @@ _SIGS = {
                                            ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mvr_pair_information": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_int,
                                      ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mvr_compute_fpfh_workspace_bytes": (c_size, [c_i64]),
+    "mvr_compute_fpfh": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_vp,
+                                 c_vp, c_vp, c_size, c_vp]),
+    "mvr_feat_match": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "mvr_posegraph_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "mvr_posegraph_optimize": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                        c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp,

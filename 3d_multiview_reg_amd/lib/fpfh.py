@@ -1,0 +1,114 @@
+"""Weights-free global registration: FPFH descriptors (csrc/fpfh.hip mvr_compute_fpfh, FragmentOverlap.compute_fpfh),
+nearest neighbours in feature space (csrc/feat_match.hip mvr_feat_match) and the batched RANSAC (mvr_ransac,
+lib.utils.run_ransac_batch); DESIGN.md 4.24, the semantics are in include/mvreg.h.
+
+What Open3D users write as compute_fpfh_feature + registration_ransac_based_on_feature_matching, for every pair of a
+scene at once and without a pretrained network: a coarse estimate that feeds lib.icp.icp_refine / gicp_refine and
+lib.multiview.synchronize unchanged.  Restated from the maths; Open3D parity is unpinned.
+
+Convention: T maps source coordinates into the target's frame, x_target ~ T x_source (lib/icp.py)."""
+import numpy as np
+import torch
+
+from lib import _native as N
+from lib.utils import RANSAC_DIST, RANSAC_ITERS, RANSAC_N, run_ransac_batch
+
+MAX_CHANNELS = 64
+
+
+def _check_inputs(name, feats, off, pairs):
+    if not torch.is_tensor(feats) or feats.dim() != 2 or feats.dtype != torch.float32:
+        raise ValueError("%s: feats must be a fp32 [M,C] tensor" % name)
+    if not 1 <= feats.shape[1] <= MAX_CHANNELS:
+        raise ValueError("%s: %d channels; mvr_feat_match takes 1..%d" % (name, feats.shape[1], MAX_CHANNELS))
+    off = np.asarray(off, dtype=np.int64).reshape(-1)
+    if len(off) < 2 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != feats.shape[0]:
+        raise ValueError("%s: off must be the [B+1] prefix sums of the fragments' sizes, ending at M" % name)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= len(off) - 1):
+        raise ValueError("%s: pairs holds a fragment index outside [0, %d)" % (name, len(off) - 1))
+    return off, pairs
+
+
+def feat_match(feats, off, pairs):
+    """mvr_feat_match: for every row of a pair's query fragment the nearest row of its target fragment in feature
+    space.  feats fp32 [M,C] on the device (C <= 64), off [B+1] host, pairs [P,2] (query fragment, target fragment).
+    -> (idx int32 [Q] device: rows within the target fragment, -1 for an empty target; dist2 fp32 [Q] device;
+    qoff int64 [P+1] numpy: pair p's queries are idx[qoff[p]:qoff[p+1]])"""
+    off, pairs = _check_inputs("feat_match", feats, off, pairs)
+    N.require_hip(feats)
+    feats = feats.contiguous()
+    dev = feats.device
+    P = len(pairs)
+    nq = np.diff(off)[pairs[:, 0]] if P else np.zeros(0, np.int64)
+    qoff = np.concatenate([[0], np.cumsum(nq)]).astype(np.int64)
+    Q = int(qoff[-1])
+    idx = torch.empty(Q, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(Q, dtype=torch.float32, device=dev)
+    if Q:
+        g_off, g_pairs, g_qoff = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (off, pairs, qoff))
+        N.check(N.lib().mvr_feat_match(N.ptr(feats), int(feats.shape[1]), N.ptr(g_off), len(off) - 1,
+                                       int(feats.shape[0]), N.ptr(g_pairs), N.ptr(g_qoff), P, Q, int(nq.max()),
+                                       N.ptr(idx), N.ptr(dist2), N.stream()), "mvr_feat_match")
+    return idx, dist2, qoff
+
+
+def match_features(feats, off, pairs, mutual=True):
+    """Feature matches of every pair: mvr_feat_match source -> target and, with `mutual`, target -> source, keeping a
+    match (i, j) only where j's nearest source row is i again.  feats, off, pairs as feat_match, pairs being
+    (source, target).  -> a list of P int64 [n_p,2] device tensors of (source row, target row) within their
+    fragments, ascending in the source row."""
+    off, pairs = _check_inputs("match_features", feats, off, pairs)
+    if len(pairs) == 0:
+        return []
+    idx_st, _, qoff = feat_match(feats, off, pairs)
+    dev = feats.device
+    P = len(pairs)
+    n_src = torch.from_numpy(np.diff(qoff)).to(dev)
+    pair_of = torch.repeat_interleave(torch.arange(P, device=dev), n_src)
+    src_row = torch.arange(int(qoff[-1]), device=dev) - torch.from_numpy(qoff[:-1]).to(dev)[pair_of]
+    tgt_row = idx_st.to(torch.int64)
+    keep = tgt_row >= 0
+    if mutual:
+        idx_ts, _, roff = feat_match(feats, off, pairs[:, ::-1])
+        back = torch.full_like(tgt_row, -1)
+        at = torch.from_numpy(roff[:-1]).to(dev)[pair_of] + tgt_row
+        back[keep] = idx_ts.to(torch.int64)[at[keep]]
+        keep = keep & (back == src_row)
+    both = torch.stack([src_row[keep], tgt_row[keep]], 1)
+    counts = torch.bincount(pair_of[keep], minlength=P).cpu().tolist() if P else []
+    return list(torch.split(both, counts))
+
+
+def register_fpfh(fo, pairs, mutual=True, seed=0, ransac_n=RANSAC_N, max_dist=RANSAC_DIST, iters=RANSAC_ITERS):
+    """Coarse registration of every pair of `fo` (a lib.overlap.FragmentOverlap after compute_fpfh()) from its FPFH
+    matches: match_features, then lib.utils.run_ransac_batch over the matched points (its defaults: 4-point
+    hypotheses, inliers within 0.05, 2500 iterations, draws keyed by `seed`).  pairs [P,2] (source, target).
+    -> dict of numpy T fp64 [P,4,4] (x_target ~ T x_source; identity where a pair has fewer than ransac_n matches or
+    no hypothesis has an inlier), fitness, rmse fp64 [P] (over the matches), n_matches int64 [P]."""
+    if getattr(fo, "fpfh", None) is None:
+        raise ValueError("register_fpfh: needs fo.fpfh (call fo.compute_fpfh())")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    matches = match_features(fo.fpfh, fo.off, pairs, mutual)
+    P = len(pairs)
+    counts = np.array([len(m) for m in matches], dtype=np.int64)
+    xyz_s, xyz_t = correspondences(fo, pairs, matches)
+    if P == 0:
+        return {"T": np.zeros((0, 4, 4)), "fitness": np.zeros(0), "rmse": np.zeros(0), "n_matches": counts}
+    T, fit, rmse, _ = run_ransac_batch(xyz_s, xyz_t, counts, seed=seed, ransac_n=ransac_n, max_dist=max_dist,
+                                       iters=iters, device=fo.device, return_all=True)
+    return {"T": T, "fitness": fit, "rmse": rmse, "n_matches": counts}
+
+
+def correspondences(fo, pairs, matches):
+    """The matched points of every pair, padded to the longest list: (source xyz, target xyz) fp64 [P,n,3] on the
+    device, rows beyond a pair's count zero (the input of lib.utils.run_ransac_batch with counts)."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    P = len(pairs)
+    n = max([len(m) for m in matches] + [1])
+    xyz_s = torch.zeros(P, n, 3, dtype=torch.float64, device=fo.device)
+    xyz_t = torch.zeros(P, n, 3, dtype=torch.float64, device=fo.device)
+    for p, m in enumerate(matches):
+        xyz_s[p, :len(m)] = fo.xyz[int(fo.off[pairs[p, 0]]) + m[:, 0]]
+        xyz_t[p, :len(m)] = fo.xyz[int(fo.off[pairs[p, 1]]) + m[:, 1]]
+    return xyz_s, xyz_t

@@ -71,6 +71,7 @@ class FragmentOverlap(object):
                                          ib, N.stream()), "mvr_radius_index_build")
         self.device = dev
         self.normals = self.n_nbr = None   # set by estimate_normals, or normals assigned by the caller
+        self.fpfh = None                   # set by compute_fpfh
 
     def estimate_normals(self, radius=None, viewpoints=None):
         """Per-point normals of every fragment (csrc/normals.hip mvr_estimate_normals: Open3D's estimate_normals with
@@ -96,6 +97,33 @@ class FragmentOverlap(object):
                                              N.ptr(normals), N.ptr(n_nbr), N.stream()), "mvr_estimate_normals")
         self.normals, self.n_nbr = normals, n_nbr
         return normals
+
+    def compute_fpfh(self, radius=None):
+        """FPFH descriptors of every point (csrc/fpfh.hip mvr_compute_fpfh: Open3D's compute_fpfh_feature with a radius
+        search, restated; the semantics are in include/mvreg.h) over the neighbours of the same fragment closer than
+        `radius` (None: fo.r; at most fo.r).  Needs fo.normals (from estimate_normals or assigned by the caller);
+        their sign matters, so orient them, e.g. with estimate_normals(viewpoints=...).
+        Stores and returns fo.fpfh (fp32 [M,33], device, the row order of fo.xyz)."""
+        radius = float(self.r if radius is None else radius)
+        if not 0.0 < radius <= self.r:
+            raise ValueError("compute_fpfh: radius %g must lie in (0, %g], the index's cell size (build the "
+                             "FragmentOverlap with radius >= it)" % (radius, self.r))
+        nrm = self.normals
+        if nrm is None:
+            raise ValueError("compute_fpfh: needs fo.normals (call fo.estimate_normals(viewpoints=...))")
+        if not torch.is_tensor(nrm) or tuple(nrm.shape) != (self.M, 3) or nrm.dtype != torch.float64 or \
+                nrm.device != self.xyz.device or not nrm.is_contiguous():
+            raise ValueError("compute_fpfh: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
+                             % self.M)
+        L = N.lib()
+        fpfh = torch.empty(self.M, 33, dtype=torch.float32, device=self.device)
+        ws_b = L.mvr_compute_fpfh_workspace_bytes(self.M)
+        ws = N.workspace(ws_b, self.device)
+        N.check(L.mvr_compute_fpfh(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(nrm),
+                                   N.ptr(self.off_dev), self.B, self.M, self.r, radius, N.ptr(fpfh), None, N.ptr(ws),
+                                   ws_b, N.stream()), "mvr_compute_fpfh")
+        self.fpfh = fpfh
+        return fpfh
 
     def counts(self, pairs, trans):
         """pairs [P, 2] fragment indices, trans [P, 4, 4] (the `trans` argument of the reference) ->

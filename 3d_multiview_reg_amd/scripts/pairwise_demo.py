@@ -9,6 +9,11 @@ and skipped.
 
 usage: python -m scripts.pairwise_demo configs/pairwise_registration/demo/config.yaml \
            [--source_pc ...cloud_bin_0.ply] [--target_pc ...cloud_bin_1.ply] [--model pairwise_reg.pt] [--verbose]
+
+--fpfh registers the pair without any network or checkpoint (lib/fpfh.py): voxel centroids at the
+config's voxel_size, normals oriented to each cloud's mean, FPFH descriptors, mutual feature matches, RANSAC and,
+with --icp, a point-to-point ICP refinement; T is printed and written to the same est_T.log.
+    [--fpfh [--fpfh_radius R] [--normal_radius R] [--icp]]   (defaults: 5 and 2 voxel sizes)
 """
 import argparse
 import logging
@@ -38,7 +43,52 @@ def prepare_data(point_cloud_files, voxel_size, device):
             "pts_list": torch.tensor(counts)}
 
 
+def _write(est_T, args):
+    """est_T.log in the reference's place -> its path"""
+    target_base = "./data/demo/pairwise/results"
+    id_0 = args.source_pc.split(os.sep)[-1].split("_")[-1].split(".")[0]
+    id_1 = args.target_pc.split(os.sep)[-1].split("_")[-1].split(".")[0]
+    os.makedirs(target_base, exist_ok=True)
+    target_path = os.path.join(target_base, "est_T.log")
+    write_trajectory(np.expand_dims(est_T, 0), [[id_0, id_1, "True"]], target_path)
+    return target_path
+
+
+def main_fpfh(cfg, args, logger=logging.getLogger()):
+    """--fpfh: FPFH + RANSAC (+ ICP) on the two clouds' voxel centroids; no model, no checkpoint"""
+    from lib.fpfh import register_fpfh
+    from lib.icp import icp_refine
+    from lib.overlap import FragmentOverlap
+    voxel = float(cfg["misc"]["voxel_size"])
+    r_fpfh = 5.0 * voxel if args.fpfh_radius is None else args.fpfh_radius
+    r_normal = 2.0 * voxel if args.normal_radius is None else args.normal_radius
+    if not (r_fpfh > 0.0 and r_normal > 0.0):
+        raise ValueError("--fpfh_radius and --normal_radius must be positive")
+    t0 = time.time()
+    raw = [read_ply_xyz(f) for f in (args.source_pc, args.target_pc)]
+    fo = FragmentOverlap(raw, "FCGF", voxel, radius=max(r_fpfh, r_normal))
+    xyz = fo.xyz.cpu().numpy()
+    fo.estimate_normals(r_normal, viewpoints=[xyz[fo.off[b]:fo.off[b + 1]].mean(0) for b in range(2)])
+    fo.compute_fpfh(r_fpfh)
+    out = register_fpfh(fo, [[0, 1]])
+    est_T = out["T"][0]
+    logger.info("FPFH + RANSAC: %d mutual matches of %d / %d points, fitness %.4f, rmse %.4f", out["n_matches"][0],
+                fo.off[1], fo.off[2] - fo.off[1], out["fitness"][0], out["rmse"][0])
+    if args.icp:
+        ref = icp_refine(fo, [[0, 1]], est_T[None], max_dist=min(fo.r, 2.0 * voxel))
+        est_T = ref["T"][0]
+        logger.info("ICP: %d iterations, fitness %.4f, rmse %.4f", ref["iters"][0], ref["fitness"][0], ref["rmse"][0])
+    target_path = _write(est_T, args)
+    print("T (source -> target):\n%s" % np.array2string(est_T, precision=8, suppress_small=True))
+    if args.verbose:
+        logger.info("Registration without a network completed in %.3fs", time.time() - t0)
+        logger.info("Estimated parameters were saved in %s.", target_path)
+    return est_T
+
+
 def main(cfg, args, logger=logging.getLogger()):
+    if getattr(args, "fpfh", False):
+        return main_fpfh(cfg, args, logger)
     np.random.seed(41)     # pairwise_demo.py:25-28 (the Sampler draws on numpy's global RandomState)
     torch.manual_seed(41)
     model = config.get_model(cfg)
@@ -85,6 +135,10 @@ def parser():
     ap.add_argument("--model", default="pairwise_reg.pt", type=str, help="Name of the pretrained model.")
     ap.add_argument("--verbose", action="store_true", help="Write out the intermediate results and timings")
     ap.add_argument("--visualize", action="store_true", help="Visualize the point cloud and the results.")
+    ap.add_argument("--fpfh", action="store_true", help="Register with FPFH + RANSAC: no network, no checkpoint.")
+    ap.add_argument("--fpfh_radius", default=None, type=float, help="FPFH support radius (default 5 voxel sizes).")
+    ap.add_argument("--normal_radius", default=None, type=float, help="Normal radius (default 2 voxel sizes).")
+    ap.add_argument("--icp", action="store_true", help="With --fpfh: refine the estimate by point-to-point ICP.")
     return ap
 
 

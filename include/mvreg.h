@@ -291,8 +291,8 @@ int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_
                         size_t workspace_bytes, double* out_xyz, int64_t* out_off, mvr_stream_t stream);
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
- * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane and
- * mvr_icp_refine_generalized calls on the same points.  B < 32768.
+ * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane,
+ * mvr_icp_refine_generalized and mvr_compute_fpfh calls on the same points.  B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
  * cells of a fragment form one run of the sorted order under one hash entry, a query walks the whole run, and
@@ -453,6 +453,58 @@ int mvr_icp_refine_generalized(const void* index, size_t index_bytes, const doub
 int mvr_pair_information(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
                          int64_t M, double r_index, const int64_t* pairs, const double* T, int P, double max_dist,
                          double* info, int32_t* n_corr, double* rmse, int32_t* status, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * FPFH descriptors on a radius index (csrc/fpfh.hip): the Fast Point Feature Histogram of Rusu et
+ * al., what Open3D's compute_fpfh_feature(KDTreeSearchParamRadius(radius)) and PCL's FPFHEstimation give, restated
+ * from the maths; Open3D / PCL parity is unpinned.  tests/fpfh_oracle.py is the numpy restatement.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`;
+ *   normals [M,3] fp64 in the row order of xyz, taken as given (not renormalised).  Their SIGN MATTERS here, unlike
+ *   for the ICPs: orient them consistently, e.g. with the viewpoints of mvr_estimate_normals.
+ *   Neighbours of point i: the points j != i (by row, so a coincident point is one) of its own fragment with
+ *   sqrt(ex*ex + ey*ey + ez*ez) < radius (strict, the expression of mvr_estimate_normals), e = x_j - x_i; k_i their
+ *   number.
+ *   Pair feature of (i, j): d = |e|, a1 = n_i . e / d, a2 = n_j . e / d.  If |a1| < |a2| the roles swap:
+ *   (n_a, n_b, e, f2) = (n_j, n_i, -e, -a2), otherwise (n_i, n_j, e, a1).  v = (e x n_a) / |e x n_a|, w = n_a x v,
+ *   f0 = atan2(w . n_b, n_a . n_b), f1 = v . n_b.  A neighbour with d == 0 or |e x n_a| == 0 adds nothing to the
+ *   histogram but still counts in k_i.
+ *   Bins, eleven per feature, each index clamped to [0, 10]: floor(11 (f0 + pi) / (2 pi)) in bins 0..10,
+ *   floor(11 (f1 + 1) / 2) in bins 11..21, floor(11 (f2 + 1) / 2) in bins 22..32.
+ *   SPFH: spfh_i[c] = 100 count_i[c] / k_i from integer counts (independent of the order of the neighbours); zeros
+ *   when k_i == 0.
+ *   FPFH: acc[c] = sum over the neighbours with d > 0 of spfh_j[c] / d^2 (d^2 = ex*ex + ey*ey + ez*ez); each of the
+ *   three groups of 11 of acc with a positive sum is scaled to sum to 100; fpfh_i = acc + spfh_i.  Geometry and
+ *   accumulation are fp64; the outputs are rounded to fp32 once.
+ *   fpfh [M,33] and spfh_out [M,33] (may be NULL) in the row order of xyz; every row is written.  Two launches (SPFH,
+ *   then FPFH) with the fp64 SPFH rows in `workspace` (>= mvr_compute_fpfh_workspace_bytes(M)); one thread per
+ *   point, no atomics; a point's outputs are a function of its fragment alone.
+ *   MVR_EINVAL, scalars first: the rules of mvr_estimate_normals (radius > r_index among them).  M == 0 then returns
+ *   MVR_OK.  With M > 0: a NULL index, xyz, off, normals, fpfh or workspace, index_bytes <
+ *   mvr_radius_index_bytes(M), or workspace_bytes < mvr_compute_fpfh_workspace_bytes(M).
+ * ---------------------------------------------------------------------- */
+size_t mvr_compute_fpfh_workspace_bytes(int64_t M);
+int mvr_compute_fpfh(const void* index, size_t index_bytes, const double* xyz, const double* normals,
+                     const int64_t* off, int B, int64_t M, double r_index, double radius, float* fpfh,
+                     float* spfh_out, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Nearest neighbour in feature space between ragged fragments (csrc/feat_match.hip), for any channel
+ * count 1 <= C <= 64 (mvr_feat_knn2 is the MFMA kernel for C == 32 and equal-sized sampled sets).
+ *   F [M,C] fp32 with row stride C, fragments off [B+1] (device); pairs [P,2] (device): (query fragment, target
+ *   fragment); qoff [P+1] (device): the prefix sums of the query fragments' sizes, computed by the caller on the host,
+ *   who passes n_queries == qoff[P] and max_q == the largest query fragment of a pair (they size the launch).
+ *   For query row i of pair p: idx[qoff[p] + i] = the row within the target fragment that minimises
+ *   sum_c (a_c - b_c)^2, accumulated in fp32 over c ascending; ties go to the smallest row; dist2 (may be NULL) that
+ *   sum.  An empty target fragment gives -1 (dist2 +inf); so does a pair with a fragment index outside [0, B), and a
+ *   query row beyond the query fragment's size where qoff disagrees with off.  Plain fp32 vector arithmetic, no
+ *   MFMA, no atomics, no workspace: a query's outputs are a function of its pair alone.
+ *   MVR_EINVAL, scalars first: C outside 1..64; negative P, M, n_queries or max_q; B <= 0 or B >= 32768;
+ *   M >= 2^31; max_q > 65535 * 256.  P == 0 or n_queries == 0 then returns MVR_OK.  Otherwise a NULL F, off, pairs,
+ *   qoff or idx, or max_q == 0.
+ * ---------------------------------------------------------------------- */
+int mvr_feat_match(const float* F, int C, const int64_t* off, int B, int64_t M, const int64_t* pairs,
+                   const int64_t* qoff, int P, int64_t n_queries, int64_t max_q, int32_t* idx, float* dist2,
+                   mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Pose-graph refinement over SE(3), batched over scenes (csrc/posegraph.hip): the Levenberg-
