@@ -122,6 +122,9 @@ _SIGS = {
     "mvr_posegraph_optimize": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                        c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp,
                                        c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "mvr_fuse_scene_workspace_bytes": (c_size, [c_i64]),
+    "mvr_fuse_scene": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, ctypes.c_double, c_vp, c_size, c_vp, c_vp,
+                               c_vp, c_vp, c_vp, c_vp]),
     "mvr_hash_table_bytes": (c_size, [c_i64]),
     "mvr_voxelize_workspace_bytes": (c_size, [c_i64]),
     "mvr_voxelize_hint_workspace_bytes": (c_size, [c_i64, c_i64]),

@@ -4,10 +4,14 @@
 an eigenproblem for the rotations, a linear solve for the translations) with optional IRLS, on the GPU
 (csrc/sync.hip mvr_sync_poses; the maths and the conventions are in DESIGN.md 4.18).  The
 reference never released this stage, so there is no reference module behind this file.
+`optimize_pose_graph` refines those poses over SE(3) (csrc/posegraph.hip), `fuse_scene` maps the fragments
+by them and merges the points per voxel into the registered scene (csrc/fuse.hip mvr_fuse_scene), and
+`register_scene` composes the library's stages from fragments to that scene without a pretrained network.
 
 Conventions: edge k = (i, j) with x_j ~ R_k x_i + t_k (source i, target j: lib.utils.pair_index order, the rot_est /
 trans_est of filter_correspondences); pose (R_i, t_i) maps fragment i into the anchor's frame, X = R_i x_i + t_i.
 """
+import numpy as np
 import torch
 
 from lib import _native as N
@@ -278,3 +282,174 @@ def weights_from_scores(scores, threshold=0.5):
     share of correspondences whose score exceeds `threshold`.  A heuristic that stands in for the paper's learned
     pair confidence — it is not a reproduction of it.  One expression on the scores' device."""
     return (scores > threshold).to(torch.float64).mean(dim=-1)
+
+
+MAX_FUSE_VOXELS_PER_AXIS = (1 << 21) - 1   # largest 21-bit voxel index of mvr_fuse_scene (include/mvreg.h)
+
+
+def _fuse_arguments(B, R, t, voxel_size, member, min_frags, min_points):
+    """fuse_scene's checks that need no device -> (R [B,3,3], t [B,3], member [B] or None) as torch tensors where
+    they were"""
+    if not (float(voxel_size) > 0.0 and float(voxel_size) < float("inf")):
+        raise ValueError("fuse_scene: voxel_size must be positive and finite")
+    if int(min_frags) < 1 or int(min_points) < 1:
+        raise ValueError("fuse_scene: min_frags and min_points must be at least 1")
+    R, t = torch.as_tensor(R), torch.as_tensor(t)
+    if tuple(R.shape) != (B, 3, 3) or not R.is_floating_point():
+        raise ValueError("fuse_scene: R must be a float [%d,3,3], one rotation per fragment" % B)
+    if tuple(t.shape) not in ((B, 3), (B, 3, 1)) or not t.is_floating_point():
+        raise ValueError("fuse_scene: t must be a float [%d,3] (or [%d,3,1]), one translation per fragment" % (B, B))
+    if not (bool(torch.isfinite(R).all()) and bool(torch.isfinite(t).all())):
+        raise ValueError("fuse_scene: R and t must be finite")
+    if member is not None:
+        member = torch.as_tensor(member)
+        if tuple(member.shape) != (B,) or member.is_floating_point() or member.is_complex():
+            raise ValueError("fuse_scene: member must be a bool or integer [%d], one flag per fragment" % B)
+    return R, t.reshape(B, 3), member
+
+
+def fuse_scene(fo, R, t, voxel_size, member=None, min_frags=1, min_points=1, normals=None):
+    """The registered scene as one cloud (csrc/fuse.hip mvr_fuse_scene): the points of `fo` (a
+    lib.overlap.FragmentOverlap) mapped by the fragments' poses and merged per voxel of `voxel_size`.  The place of
+    Open3D's `pcd_combined += pcd.transform(pose)` and voxel_down_sample; Open3D parity is unpinned.
+
+    R [B,3,3], t [B,3] (or [B,3,1]): pose of every fragment, X = R_b x + t_b (what synchronize and
+    optimize_pose_graph return), numpy or torch, any float dtype.  member [B] (bool or integer, None: all): a zero
+    leaves the fragment out (pass the `member` synchronize returned).  normals None: fo.normals when it is set;
+    False: fuse without normals; a contiguous fp64 [M,3] device tensor: those.  Normals are averaged as they are, so
+    their orientation matters (fo.estimate_normals(viewpoints=...)).
+    min_frags / min_points keep the voxels that at least so many distinct fragments / points fell into (a voxel seen
+    by one fragment only is the usual sign of a misregistered fragment or of clutter); the rows are filtered on the
+    device.
+    Returns a dict of xyz fp64 [V,3] (device; ascending voxel key), normals fp64 [V,3] or None, n_points and n_frags
+    int32 [V], voxel_size."""
+    R, t, member = _fuse_arguments(fo.B, R, t, voxel_size, member, min_frags, min_points)
+    nrm = getattr(fo, "normals", None) if normals is None else (None if normals is False else normals)
+    if nrm is not None and (not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64
+                            or nrm.device != fo.xyz.device or not nrm.is_contiguous()):
+        raise ValueError("fuse_scene: normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz" % fo.M)
+    N.require_hip()
+    dev, M, voxel = fo.device, int(fo.M), float(voxel_size)
+    poses = torch.cat([R.to(dev, torch.float64), t.to(dev, torch.float64).unsqueeze(-1)], 2).reshape(fo.B, 12)
+    poses = poses.contiguous()
+    mem = None if member is None else (member != 0).to(dev, torch.uint8).contiguous()
+    cap = max(M, 1)
+    xyz = torch.empty(cap, 3, dtype=torch.float64, device=dev)
+    out_n = torch.empty(cap, 3, dtype=torch.float64, device=dev) if nrm is not None else None
+    n_points, n_frags = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2))
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    L = N.lib()
+    ws_b = L.mvr_fuse_scene_workspace_bytes(M)
+    ws = N.workspace(ws_b, dev)
+    N.check(L.mvr_fuse_scene(N.ptr(fo.xyz), N.ptr(nrm), N.ptr(fo.off_dev), fo.B, M, N.ptr(poses), N.ptr(mem), voxel,
+                             N.ptr(ws), ws_b, N.ptr(xyz), N.ptr(out_n), N.ptr(n_points), N.ptr(n_frags),
+                             N.ptr(count), N.stream()), "mvr_fuse_scene")
+    V = int(count.item())   # set on the device by mvr_fuse_scene: no synchronisation beyond this copy
+    if V < 0:
+        raise ValueError("fuse_scene: the posed scene spans more than %d voxels of size %g along an axis (voxel "
+                         "indices are 21-bit, so an extent of at most %g), or a mapped point is not finite; use a "
+                         "larger voxel_size or leave the stray fragment out with `member`"
+                         % (MAX_FUSE_VOXELS_PER_AXIS, voxel, MAX_FUSE_VOXELS_PER_AXIS * voxel))
+    xyz, n_points, n_frags = xyz[:V], n_points[:V], n_frags[:V]
+    out_n = None if out_n is None else out_n[:V]
+    if int(min_frags) > 1 or int(min_points) > 1:
+        keep = (n_frags >= int(min_frags)) & (n_points >= int(min_points))
+        xyz, n_points, n_frags = xyz[keep], n_points[keep], n_frags[keep]
+        out_n = None if out_n is None else out_n[keep]
+    return {"xyz": xyz, "normals": out_n, "n_points": n_points, "n_frags": n_frags, "voxel_size": voxel}
+
+
+OVERLAP_THRESHOLDS = {"3d_match": 0.3, "redwood": 0.23}   # scripts/benchmark_pairwise_registration.py --dataset
+ICP_METHODS = ("point_to_point", "point_to_plane", "generalized")
+
+
+def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
+    """register_scene's checks that need no device -> (pairs [P,2], init [P,4,4] or None, viewpoints [n,3])"""
+    if n < 2:
+        raise ValueError("register_scene: needs at least two fragments")
+    if n > MAX_FRAGS:
+        raise ValueError("register_scene: at most %d fragments per scene" % MAX_FRAGS)
+    if not (float(voxel_size) > 0.0 and float(voxel_size) < float("inf")):
+        raise ValueError("register_scene: voxel_size must be positive and finite")
+    if method not in ICP_METHODS:
+        raise ValueError("register_scene: method must be one of %s, not %r" % (", ".join(ICP_METHODS), method))
+    if dataset not in OVERLAP_THRESHOLDS:
+        raise ValueError("register_scene: dataset must be one of %s, not %r"
+                         % (", ".join(sorted(OVERLAP_THRESHOLDS)), dataset))
+    pairs = np.asarray([(i, j) for i in range(n) for j in range(i + 1, n)], dtype=np.int64)
+    if init is not None:
+        init = np.asarray(init, dtype=np.float64)
+        if init.shape != (len(pairs), 4, 4) or not np.isfinite(init).all():
+            raise ValueError("register_scene: init must hold a finite 4 x 4 estimate for each of the %d pairs i < j, "
+                             "in that order" % len(pairs))
+    viewpoints = np.zeros((n, 3)) if viewpoints is None else np.asarray(viewpoints, dtype=np.float64)
+    if viewpoints.shape != (n, 3) or not np.isfinite(viewpoints).all():
+        raise ValueError("register_scene: viewpoints must be a finite [%d,3], one per fragment" % n)
+    return pairs, init, viewpoints
+
+
+def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=None, viewpoints=None, downsample=True,
+                   dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
+                   icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
+                   min_frags=1, min_points=1):
+    """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
+    composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
+      1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
+         (downsample False: the points as given on the same index);
+      2. estimate_normals(normal_radius, viewpoints) — viewpoints [n,3] in the fragments' own frames, None: their
+         origins (where a range sensor stood);
+      3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed`
+         (init [P,4,4], x_j ~ T x_i for the pairs i < j in that order, replaces 3 and 4);
+      5. the overlap gate of the pairwise benchmark: a pair is kept when FragmentOverlap.ratios >= overlap_threshold
+         (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
+      6. lib.icp.icp_refine (method 'point_to_point' / 'point_to_plane') or gicp_refine ('generalized') on the kept
+         pairs;  7. lib.icp.information_matrix;  8. synchronize(irls_iters=5);  9. optimize_pose_graph with the
+         IRLS weights;  10. fuse_scene(voxel fuse_voxel, None: voxel_size) over the fragments connected to `anchor`.
+    Returns a dict of R [n,3,3], t [n,3] and poses [n,4,4] (numpy fp64, fragment -> the anchor's frame), member [n],
+    pairs: a dict of numpy arrays over the pairs i < j (pairs [P,2], T_coarse [P,4,4], overlap [P], kept bool [P],
+    T [P,4,4] the refined estimate (the coarse one where the pair was not kept), fitness and rmse [P] of the
+    refinement, 0 where not kept), sync and refined (the dicts of synchronize and optimize_pose_graph), fo, and
+    scene (the dict of fuse_scene)."""
+    from lib.fpfh import register_fpfh
+    from lib.icp import gicp_refine, icp_refine, information_matrix
+    from lib.overlap import FragmentOverlap
+    n = len(xyz_list)
+    pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints)
+    threshold = OVERLAP_THRESHOLDS[dataset] if overlap_threshold is None else float(overlap_threshold)
+    P = len(pairs)
+    if downsample:
+        fo = FragmentOverlap(xyz_list, "FCGF", voxel_size)
+    else:
+        fo = FragmentOverlap(xyz_list, "3DMatch", radius=3.0 * float(voxel_size))
+    fo.estimate_normals(normal_radius, viewpoints)
+    if init is None:
+        fo.compute_fpfh(fpfh_radius)
+        T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed)["T"], dtype=np.float64)
+    else:
+        T_coarse = init
+    overlap = fo.ratios(pairs, np.linalg.inv(T_coarse))      # the gate's `trans` is the inverse of the estimate
+    kept = overlap >= threshold
+    kp = pairs[kept]
+    if method == "generalized":
+        ref = gicp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, epsilon=gicp_epsilon)
+    else:
+        ref = icp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, method=method)
+    Tk = np.asarray(ref["T"], dtype=np.float64).reshape(-1, 4, 4)
+    info = information_matrix(fo, kp, Tk, max_dist=icp_max_dist)
+    sync = synchronize(Tk[:, :3, :3], Tk[:, :3, 3], kp, n, anchor=anchor, irls_iters=5)
+    refined = optimize_pose_graph(np.asarray(sync["R"]), np.asarray(sync["t"]), Tk[:, :3, :3], Tk[:, :3, 3], kp,
+                                  np.asarray(info["info"]), np.asarray(sync["weights"]), anchor=anchor,
+                                  max_iters=refine_iters)
+    R, t = np.asarray(refined["R"], dtype=np.float64), np.asarray(refined["t"], dtype=np.float64)
+    member = np.asarray(refined["member"])
+    scene = fuse_scene(fo, R, t, voxel_size if fuse_voxel is None else fuse_voxel, member=member,
+                       min_frags=min_frags, min_points=min_points)
+    poses = np.tile(np.eye(4), (n, 1, 1))
+    poses[:, :3, :3], poses[:, :3, 3] = R, t
+    T = T_coarse.copy()
+    fitness, rmse = np.zeros(P), np.zeros(P)
+    T[kept], fitness[kept], rmse[kept] = Tk, np.asarray(ref["fitness"]), np.asarray(ref["rmse"])
+    records = {"pairs": pairs, "T_coarse": T_coarse, "overlap": overlap, "kept": kept, "T": T, "fitness": fitness,
+               "rmse": rmse}
+    return {"R": R, "t": t, "poses": poses, "member": member, "pairs": records, "sync": sync, "refined": refined,
+            "fo": fo, "scene": scene}

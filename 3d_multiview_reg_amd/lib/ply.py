@@ -53,3 +53,20 @@ def write_ply_xyz(path, xyz):
         f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
                  "property float z\nend_header\n" % len(xyz)).encode())
         f.write(xyz.tobytes())
+
+
+def write_ply(path, xyz, normals=None):
+    """Points [N,3] and, when given, their normals [N,3] as little-endian float properties x y z (nx ny nz); the
+    file reads back through read_ply_xyz, which picks x, y, z by name."""
+    xyz = np.asarray(xyz, dtype="<f4").reshape(-1, 3)
+    cols, names = [xyz], ["x", "y", "z"]
+    if normals is not None:
+        normals = np.asarray(normals, dtype="<f4").reshape(-1, 3)
+        if len(normals) != len(xyz):
+            raise ValueError("write_ply: %d normals for %d points" % (len(normals), len(xyz)))
+        cols, names = [xyz, normals], names + ["nx", "ny", "nz"]
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%send_header\n"
+                 % (len(xyz), "".join("property float %s\n" % n for n in names))).encode())
+        f.write(np.ascontiguousarray(np.concatenate(cols, 1)).tobytes())
+

@@ -1,0 +1,97 @@
+"""Fragments in, registered scene out, without a pretrained network: PLY files -> poses.txt, traj.txt, scene.ply.
+
+lib.multiview.register_scene on the fragments' PLY files: voxel centroids, normals, FPFH + RANSAC on all pairs
+(or the pairwise estimates of --init), the overlap gate, ICP, information matrices, synchronisation, pose-graph
+refinement and the fused cloud, all on the GPU.  Writes into --out
+  poses.txt   one block per fragment: `i i N` and the 4 x 4 pose M_i (fragment i -> the anchor's frame),
+  traj.txt    the pairs that passed the overlap gate, `i j True` and inv(T) of the refined estimate x_j ~ T x_i (the
+              3DMatch log convention of the pairwise benchmark's traj.txt, readable by scripts/multiview_sync.py),
+  scene.ply   the fused cloud with normals (scripts/fuse_scene.py fuses again at another voxel size from poses.txt).
+--init traj.txt: a trajectory in that convention holding every pair i < j replaces the FPFH stage.
+
+usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
+           [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+from lib.ply import read_ply_xyz, write_ply  # noqa: E402
+from lib.utils import ensure_dir, read_trajectory, write_trajectory  # noqa: E402
+from scripts.multiview_sync import write_poses  # noqa: E402
+
+ICP_METHODS = ("point_to_point", "point_to_plane", "generalized")   # lib.multiview.ICP_METHODS
+DATASETS = ("3d_match", "redwood")                                  # lib.multiview.OVERLAP_THRESHOLDS
+
+
+def read_init(filename, n_fragments):
+    """a traj.txt (T_log = inv(T)) holding every pair i < j -> [P,4,4] estimates x_j ~ T x_i in the order of the
+    pairs i < j"""
+    keys, traj = read_trajectory(filename)
+    by_pair = {(int(k[0]), int(k[1])): np.linalg.inv(T) for k, T in zip(keys, traj)}
+    want = [(i, j) for i in range(n_fragments) for j in range(i + 1, n_fragments)]
+    missing = [p for p in want if p not in by_pair]
+    if missing:
+        raise ValueError("%s: no estimate for the pairs %s" % (filename, missing[:8]))
+    return np.asarray([by_pair[p] for p in want], dtype=np.float64).reshape(-1, 4, 4)
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--fragments", required=True, nargs="+", help="the fragments' PLY files (at least two)")
+    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--voxel_size", type=float, default=0.025, help="voxel size of the centroids and of the scene")
+    ap.add_argument("--icp_method", default="point_to_point", choices=ICP_METHODS)
+    ap.add_argument("--init", default=None, help="traj.txt with an estimate for every pair i < j instead of FPFH")
+    ap.add_argument("--dataset", default="3d_match", choices=DATASETS,
+                    help="the overlap gate's threshold, as the pairwise benchmark picks it: 0.3 / 0.23")
+    ap.add_argument("--min_frags", type=int, default=1, help="keep the voxels at least so many fragments fell into")
+    ap.add_argument("--anchor", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=0, help="RANSAC draw stream seed")
+    return ap
+
+
+def check_args(ap, a):
+    if len(a.fragments) < 2:
+        ap.error("--fragments needs at least two files")
+    if not a.voxel_size > 0.0:
+        ap.error("--voxel_size must be positive")
+    if a.min_frags < 1:
+        ap.error("--min_frags must be at least 1")
+    if not 0 <= a.anchor < len(a.fragments):
+        ap.error("--anchor outside the fragments")
+    return a
+
+
+def main(argv=None):
+    from lib.multiview import register_scene
+    ap = parser()
+    a = check_args(ap, ap.parse_args(argv))
+    frags = [read_ply_xyz(f) for f in a.fragments]
+    init = None if a.init is None else read_init(a.init, len(frags))
+    res = register_scene(frags, a.voxel_size, method=a.icp_method, init=init, dataset=a.dataset, seed=a.seed,
+                         anchor=a.anchor, min_frags=a.min_frags)
+    ensure_dir(a.out)
+    write_poses(res["poses"], os.path.join(a.out, "poses.txt"))
+    rec = res["pairs"]
+    meta = [[int(i), int(j), bool(k)] for (i, j), k in zip(rec["pairs"], rec["kept"])]
+    write_trajectory(np.linalg.inv(rec["T"]), meta, os.path.join(a.out, "traj.txt"))
+    scene = res["scene"]
+    write_ply(os.path.join(a.out, "scene.ply"), scene["xyz"].cpu().numpy(),
+              None if scene["normals"] is None else scene["normals"].cpu().numpy())
+    print("registered %d fragments: %d of %d pairs passed the overlap gate, %d fragments connected to anchor %d; "
+          "pose-graph cost %.6g -> %.6g; %d voxels of %g -> %s"
+          % (len(frags), int(rec["kept"].sum()), len(meta), int(np.asarray(res["member"]).sum()), a.anchor,
+             float(res["refined"]["cost"][0]), float(res["refined"]["cost"][1]), len(scene["xyz"]), a.voxel_size,
+             a.out))
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -554,6 +554,46 @@ int mvr_posegraph_optimize(const double* R_pair, const double* t_pair, const int
                            int64_t f_sstride, int32_t* member, double* cost, int32_t* iters, int32_t* status,
                            double* trace, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Scene fusion (csrc/fuse.hip): the registered fragments mapped by their poses into one frame and
+ * merged per voxel.  What Open3D users write as `pcd_combined += pcd.transform(pose)` followed by
+ * voxel_down_sample(voxel): VoxelDownSample of the concatenated, transformed cloud, restated; Open3D parity unpinned.
+ * tests/fuse_oracle.py is the numpy restatement.
+ *   xyz [M,3], normals [M,3] (may be NULL), off [B+1] (device): the fp64 arrays of a lib.overlap.FragmentOverlap, in
+ *   its row order and with its fragment offsets.  poses [B,12]: 3x4 row-major [R | t], fragment -> scene (the poses
+ *   of mvr_sync_poses / mvr_posegraph_optimize).  member [B] (may be NULL: every fragment): 0 leaves a fragment out.
+ *   Transform: every point of a member fragment b maps to q_d = R[d][0]*x + R[d][1]*y + R[d][2]*z + t_d in fp64;
+ *   normals map by R only.
+ *   Grid: lo_d = (min over all mapped member points of q_d) - voxel/2; voxel index floor((q_d - lo_d) / voxel), the
+ *   expression of mvr_voxel_centroids.  Key: 21 bits per axis, (ix << 42) | (iy << 21) | iz.
+ *   Range: the fp64 quotient is tested before the cast.  An index outside [0, 2^21) (a scene wider than about
+ *   2,097,151.5 voxels along an axis: 52 km at voxel = 0.025) or a non-finite q makes the call return MVR_OK with
+ *   *out_count = -1; the rows are then not meaningful, and nothing is written out of bounds (the convention of
+ *   mvr_voxel_centroids' out_off[B]).  lib.multiview.fuse_scene raises ValueError on it.
+ *   Output: one row per occupied voxel in ascending key order, *out_count = V (device scalar; no synchronisation).
+ *   out_xyz [M,3] capacity: the fp64 sum of the voxel's mapped points in input order (ascending fragment, then
+ *   ascending row: the stable sort keeps it) / their count.  out_n_points [M]: that count.  out_n_frags [M]: the
+ *   number of distinct fragments among them (in that order: the fragment changes along the run, plus 1).
+ *   out_normals [M,3] (required iff normals): the sum of the rotated normals in the same order / its Euclidean norm;
+ *   an exactly zero sum gives (0, 0, 1), the convention of mvr_estimate_normals.  Normals are taken as given (not
+ *   renormalised) and their ORIENTATION MATTERS: opposite normals of one surface cancel, so orient them, e.g. with
+ *   the viewpoints of mvr_estimate_normals.
+ *   Determinism: no floating-point atomics; a minimum is exact in any order and every sum is one thread's left fold,
+ *   so the result is a function of the inputs alone, bit-identical from run to run.
+ *   Launches: transform + partial minima, origin, keys, the radix sort (64 key bits: 1 clear, 1 histogram,
+ *   8 passes), sorted keys, head flags, scan (3), run starts, count, one thread per occupied voxel over its run.
+ *   M < 2^31; B is bounded by int only (the fragment is not in the key).
+ *   MVR_EINVAL, scalars first: negative M; M >= 2^31; B <= 0; voxel not > 0; a NULL out_count.  M == 0 then returns
+ *   MVR_OK with *out_count = 0 (the point arrays and the workspace may be NULL); member fragments without a point
+ *   give 0 as well.  With M > 0: a NULL xyz, off, poses, workspace, out_xyz, out_n_points or out_n_frags,
+ *   workspace_bytes < mvr_fuse_scene_workspace_bytes(M), or exactly one of normals / out_normals given.
+ * ---------------------------------------------------------------------- */
+size_t mvr_fuse_scene_workspace_bytes(int64_t M);
+int mvr_fuse_scene(const double* xyz, const double* normals, const int64_t* off, int B, int64_t M,
+                   const double* poses, const uint8_t* member, double voxel, void* workspace, size_t workspace_bytes,
+                   double* out_xyz, double* out_normals, int32_t* out_n_points, int32_t* out_n_frags,
+                   int64_t* out_count, mvr_stream_t stream);
+
 /* Farthest point sampling per fragment (Sampler 'fps', lib/layers.py:134-141 — pointnet2
  * furthest_point_sample semantics of oracle/fps.py: seed = first point, running min of squared
  * distances, first maximum on ties).  xyz [sum n][3] with fragment row offsets (device `offsets`
