@@ -14,6 +14,7 @@
 // (+4+4 when the guard rewrites w and its copy).
 #include "common.hpp"
 #include "prof.hpp"
+#include "ransac.hpp"
 #include "svd3.hpp"
 #include <math.h>
 
@@ -165,13 +166,7 @@ __global__ __launch_bounds__(256) void procrustes_kernel(ProcrustesArgs<T> a) {
 // counts and error sums equal the host restatement's bit for bit.  A second kernel picks each pair's best.
 // Work per pair: iters x n x ~15 fp64 ops (2500 x 5000: 0.19 GFLOP) — fp64 VALU-bound.
 // ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t ransac_draw(uint64_t seed, uint64_t ctr) {
-  uint64_t z = seed + ctr * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
+// ransac_draw: ransac.hpp (shared with ransac_checked.hip)
 struct RansacArgs {
   const double* x1; const double* x2; int64_t ps;   // [P][ps] rows of 3 doubles
   const int32_t* n;                                  // [P] correspondences per pair

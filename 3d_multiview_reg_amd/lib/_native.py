@@ -54,6 +54,10 @@ _SIGS = {
     "mvr_ransac_workspace_bytes": (c_size, [c_int, c_int]),
     "mvr_ransac": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_uint64, c_vp, c_vp,
                            c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "mvr_ransac_checked_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "mvr_ransac_checked": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_uint64,
+                                   c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, ctypes.c_double, c_vp, c_vp,
+                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "mvr_sync_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "mvr_sync_poses": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
                                ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -227,6 +231,8 @@ def source_hash():
 
 PROF_KINDS = {"conv_pts": 0, "embed": 1, "pool": 2, "unpool": 3, "oafilter": 4, "small": 5, "procrustes": 6,
               "feat_nn": 7, "spconv": 8, "sparse_misc": 9, "pointcn": 10}
+# mvr_ransac_checked's four launches (csrc/prof.hpp; ids for prof_get, read by tools/ransac_micro.py --checked)
+RANSAC_CHECKED_PROF = {"check": 11, "scan": 12, "eval": 13, "select": 14}
 
 
 def prof_set(on):

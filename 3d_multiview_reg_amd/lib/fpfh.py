@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from lib import _native as N
-from lib.utils import RANSAC_DIST, RANSAC_ITERS, RANSAC_N, run_ransac_batch
+from lib.utils import RANSAC_DIST, RANSAC_ITERS, RANSAC_N, run_ransac_batch, run_ransac_checked_batch
 
 MAX_CHANNELS = 64
 
@@ -80,19 +80,42 @@ def match_features(feats, off, pairs, mutual=True):
     return list(torch.split(both, counts))
 
 
-def register_fpfh(fo, pairs, mutual=True, seed=0, ransac_n=RANSAC_N, max_dist=RANSAC_DIST, iters=RANSAC_ITERS):
+CHECKER_KEYS = ("ransac_n", "iters", "max_validation", "edge_sim", "check_dist", "normal_deg")
+
+
+def register_fpfh(fo, pairs, mutual=True, seed=0, ransac_n=RANSAC_N, max_dist=RANSAC_DIST, iters=RANSAC_ITERS,
+                  checkers=False):
     """Coarse registration of every pair of `fo` (a lib.overlap.FragmentOverlap after compute_fpfh()) from its FPFH
     matches: match_features, then lib.utils.run_ransac_batch over the matched points (its defaults: 4-point
     hypotheses, inliers within 0.05, 2500 iterations, draws keyed by `seed`).  pairs [P,2] (source, target).
     -> dict of numpy T fp64 [P,4,4] (x_target ~ T x_source; identity where a pair has fewer than ransac_n matches or
-    no hypothesis has an inlier), fitness, rmse fp64 [P] (over the matches), n_matches int64 [P]."""
+    no hypothesis has an inlier), fitness, rmse fp64 [P] (over the matches), n_matches int64 [P].
+    checkers: True, or a dict overriding some of CHECKER_KEYS, runs lib.utils.run_ransac_checked_batch instead with
+    its defaults (3-point samples, 100000 iterations of which at most 2500 are scored, the edge-length checker at
+    0.9 and the distance checker at max_dist; `ransac_n` and `iters` above are then not used); 'normal_deg' adds the
+    normal checker on fo.normals.  The dict then also holds n_pass and n_valid int32 [P]."""
     if getattr(fo, "fpfh", None) is None:
         raise ValueError("register_fpfh: needs fo.fpfh (call fo.compute_fpfh())")
+    if checkers is not False and checkers is not True:
+        if not isinstance(checkers, dict) or set(checkers) - set(CHECKER_KEYS):
+            raise ValueError("register_fpfh: checkers is a bool or a dict with keys among %s" % (CHECKER_KEYS,))
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     matches = match_features(fo.fpfh, fo.off, pairs, mutual)
     P = len(pairs)
     counts = np.array([len(m) for m in matches], dtype=np.int64)
     xyz_s, xyz_t = correspondences(fo, pairs, matches)
+    if checkers is not False:
+        opts = dict(checkers) if isinstance(checkers, dict) else {}
+        if P == 0:
+            return {"T": np.zeros((0, 4, 4)), "fitness": np.zeros(0), "rmse": np.zeros(0), "n_matches": counts,
+                    "n_pass": np.zeros(0, np.int32), "n_valid": np.zeros(0, np.int32)}
+        if opts.get("normal_deg") is not None:
+            if fo.normals is None:
+                raise ValueError("register_fpfh: the normal checker needs fo.normals")
+            opts["normals_i"], opts["normals_j"] = correspondences(fo, pairs, matches, fo.normals)
+        out = run_ransac_checked_batch(xyz_s, xyz_t, counts, seed=seed, max_dist=max_dist, device=fo.device, **opts)
+        return {"T": out["T"], "fitness": out["fitness"], "rmse": out["rmse"], "n_matches": counts,
+                "n_pass": out["n_pass"], "n_valid": out["n_valid"]}
     if P == 0:
         return {"T": np.zeros((0, 4, 4)), "fitness": np.zeros(0), "rmse": np.zeros(0), "n_matches": counts}
     T, fit, rmse, _ = run_ransac_batch(xyz_s, xyz_t, counts, seed=seed, ransac_n=ransac_n, max_dist=max_dist,
@@ -100,15 +123,17 @@ def register_fpfh(fo, pairs, mutual=True, seed=0, ransac_n=RANSAC_N, max_dist=RA
     return {"T": T, "fitness": fit, "rmse": rmse, "n_matches": counts}
 
 
-def correspondences(fo, pairs, matches):
+def correspondences(fo, pairs, matches, rows=None):
     """The matched points of every pair, padded to the longest list: (source xyz, target xyz) fp64 [P,n,3] on the
-    device, rows beyond a pair's count zero (the input of lib.utils.run_ransac_batch with counts)."""
+    device, rows beyond a pair's count zero (the input of lib.utils.run_ransac_batch with counts).  rows: another
+    fp64 [M,3] tensor in the row order of fo.xyz to gather instead (fo.normals)."""
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     P = len(pairs)
+    rows = fo.xyz if rows is None else rows
     n = max([len(m) for m in matches] + [1])
     xyz_s = torch.zeros(P, n, 3, dtype=torch.float64, device=fo.device)
     xyz_t = torch.zeros(P, n, 3, dtype=torch.float64, device=fo.device)
     for p, m in enumerate(matches):
-        xyz_s[p, :len(m)] = fo.xyz[int(fo.off[pairs[p, 0]]) + m[:, 0]]
-        xyz_t[p, :len(m)] = fo.xyz[int(fo.off[pairs[p, 1]]) + m[:, 1]]
+        xyz_s[p, :len(m)] = rows[int(fo.off[pairs[p, 0]]) + m[:, 0]]
+        xyz_t[p, :len(m)] = rows[int(fo.off[pairs[p, 1]]) + m[:, 1]]
     return xyz_s, xyz_t

@@ -391,14 +391,15 @@ def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
 def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=None, viewpoints=None, downsample=True,
                    dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
-                   min_frags=1, min_points=1):
+                   min_frags=1, min_points=1, ransac_checkers=False):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
          (downsample False: the points as given on the same index);
       2. estimate_normals(normal_radius, viewpoints) — viewpoints [n,3] in the fragments' own frames, None: their
          origins (where a range sensor stood);
-      3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed`
+      3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed` and
+         checkers=ransac_checkers (True or a dict: RANSAC with correspondence checkers and 100000 draws)
          (init [P,4,4], x_j ~ T x_i for the pairs i < j in that order, replaces 3 and 4);
       5. the overlap gate of the pairwise benchmark: a pair is kept when FragmentOverlap.ratios >= overlap_threshold
          (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
@@ -424,7 +425,7 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     fo.estimate_normals(normal_radius, viewpoints)
     if init is None:
         fo.compute_fpfh(fpfh_radius)
-        T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed)["T"], dtype=np.float64)
+        T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed, checkers=ransac_checkers)["T"], dtype=np.float64)
     else:
         T_coarse = init
     overlap = fo.ratios(pairs, np.linalg.inv(T_coarse))      # the gate's `trans` is the inverse of the estimate

@@ -387,6 +387,64 @@ def run_ransac_batch(xyz_i, xyz_j, counts=None, seed=0, ransac_n=RANSAC_N, max_d
     return T.cpu().numpy()
 
 
+def run_ransac_checked_batch(xyz_i, xyz_j, counts=None, seed=0, ransac_n=3, max_dist=RANSAC_DIST, iters=100000,
+                             max_validation=2500, edge_sim=0.9, check_dist=None, normals_i=None, normals_j=None,
+                             normal_deg=None, device=None):
+    """Batched RANSAC with correspondence checkers (csrc/ransac_checked.hip mvr_ransac_checked; the settings of
+    Open3D's global-registration examples): of `iters` samples of ransac_n correspondences, those that pass the
+    edge-length checker (edge_sim in [0, 1), 0: off), the distance checker (check_dist, None: max_dist, 0: off)
+    and, with normals_i, normals_j [P, n, 3] and normal_deg (the largest angle in degrees between a rotated source
+    normal and its target normal), the normal checker; the first max_validation of them are scored over all
+    correspondences.  xyz_i, xyz_j, counts, seed, max_dist as run_ransac_batch (the same draw stream).
+    Returns a dict of numpy arrays: T [P,4,4] fp64 (x_j ~ T x_i), fitness, rmse [P], best_iter [P] (-1: none),
+    n_pass [P] (samples that passed every checker), n_valid [P] = min(n_pass, max_validation)."""
+    from lib import _native as N
+    if (normals_i is None) != (normals_j is None) or (normals_i is None) != (normal_deg is None):
+        raise ValueError("the normal checker takes normals_i, normals_j and normal_deg together")
+    check_dist = float(max_dist if check_dist is None else check_dist)
+    if not 0.0 <= float(edge_sim) < 1.0:
+        raise ValueError("edge_sim must be in [0, 1)")
+    if not (check_dist >= 0.0 and np.isfinite(check_dist)):
+        raise ValueError("check_dist must be finite and >= 0")
+    if normal_deg is not None and not 0.0 <= float(normal_deg) <= 180.0:
+        raise ValueError("normal_deg must be in [0, 180]")
+    if int(max_validation) < 1 or int(iters) < 1:
+        raise ValueError("iters and max_validation must be at least 1")
+    N.require_hip()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    x1 = torch.as_tensor(xyz_i).to(dev, torch.float64).contiguous()
+    x2 = torch.as_tensor(xyz_j).to(dev, torch.float64).contiguous()
+    if x1.dim() != 3 or x1.shape != x2.shape or x1.shape[-1] != 3:
+        raise ValueError("xyz_i / xyz_j must both be [P, n, 3]")
+    P, n = x1.shape[0], x1.shape[1]
+    n1 = n2 = None
+    ncos = -1.0
+    if normals_i is not None:
+        n1 = torch.as_tensor(normals_i).to(dev, torch.float64).contiguous()
+        n2 = torch.as_tensor(normals_j).to(dev, torch.float64).contiguous()
+        if n1.shape != x1.shape or n2.shape != x1.shape:
+            raise ValueError("normals_i / normals_j must have the shape of xyz_i")
+        ncos = min(1.0, max(-1.0, float(np.cos(np.deg2rad(float(normal_deg))))))
+    cnt = torch.full((P,), n, dtype=torch.int32) if counts is None else torch.as_tensor(counts).to(torch.int32)
+    if cnt.numel() != P or bool((cnt < 0).any()) or bool((cnt > n).any()):
+        raise ValueError("counts must be [P] with 0 <= counts <= n")
+    cnt = cnt.to(dev)
+    iters, maxv = int(iters), min(int(max_validation), int(iters))
+    T = torch.empty(P, 4, 4, dtype=torch.float64, device=dev)
+    fit = torch.empty(P, dtype=torch.float64, device=dev)
+    rmse = torch.empty(P, dtype=torch.float64, device=dev)
+    best, n_pass, n_valid = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    L = N.lib()
+    ws = N.workspace(L.mvr_ransac_checked_workspace_bytes(P, iters, maxv), dev)
+    N.check(L.mvr_ransac_checked(N.ptr(x1), N.ptr(x2), n * 3, N.ptr(cnt), P, int(ransac_n), iters, float(max_dist),
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, maxv, float(edge_sim), check_dist, N.ptr(n1),
+                                 N.ptr(n2), ncos, N.ptr(T), N.ptr(fit), N.ptr(rmse), N.ptr(best), N.ptr(n_pass),
+                                 N.ptr(n_valid), None, None, None, N.ptr(ws), ws.numel(), N.stream()),
+            "mvr_ransac_checked")
+    return {"T": T.cpu().numpy(), "fitness": fit.cpu().numpy(), "rmse": rmse.cpu().numpy(),
+            "best_iter": best.cpu().numpy(), "n_pass": n_pass.cpu().numpy(), "n_valid": n_valid.cpu().numpy()}
+
+
 def run_ransac(xyz_i, xyz_j, seed=0):
     """utils.py:671-709: RANSAC-based estimate of the transformation mapping xyz_i [n,3] onto xyz_j [n,3]
     (correspondences are row-aligned), returned as a 4x4 float64 array.  Open3D seeds its draws from the

@@ -70,7 +70,9 @@ def main_fpfh(cfg, args, logger=logging.getLogger()):
     xyz = fo.xyz.cpu().numpy()
     fo.estimate_normals(r_normal, viewpoints=[xyz[fo.off[b]:fo.off[b + 1]].mean(0) for b in range(2)])
     fo.compute_fpfh(r_fpfh)
-    out = register_fpfh(fo, [[0, 1]])
+    out = register_fpfh(fo, [[0, 1]], checkers=bool(getattr(args, "checkers", False)))
+    if "n_pass" in out:
+        logger.info("checkers: %d of 100000 samples passed, %d scored", out["n_pass"][0], out["n_valid"][0])
     est_T = out["T"][0]
     logger.info("FPFH + RANSAC: %d mutual matches of %d / %d points, fitness %.4f, rmse %.4f", out["n_matches"][0],
                 fo.off[1], fo.off[2] - fo.off[1], out["fitness"][0], out["rmse"][0])
@@ -138,6 +140,8 @@ def parser():
     ap.add_argument("--fpfh", action="store_true", help="Register with FPFH + RANSAC: no network, no checkpoint.")
     ap.add_argument("--fpfh_radius", default=None, type=float, help="FPFH support radius (default 5 voxel sizes).")
     ap.add_argument("--normal_radius", default=None, type=float, help="Normal radius (default 2 voxel sizes).")
+    ap.add_argument("--checkers", action="store_true",
+                    help="With --fpfh: RANSAC with edge-length and distance checkers, 3-point samples, 100000 draws.")
     ap.add_argument("--icp", action="store_true", help="With --fpfh: refine the estimate by point-to-point ICP.")
     return ap
 

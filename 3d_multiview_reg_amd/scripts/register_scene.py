@@ -11,6 +11,7 @@ refinement and the fused cloud, all on the GPU.  Writes into --out
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
            [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
+           [--checkers]
 """
 import argparse
 import os
@@ -54,6 +55,8 @@ def parser():
     ap.add_argument("--min_frags", type=int, default=1, help="keep the voxels at least so many fragments fell into")
     ap.add_argument("--anchor", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0, help="RANSAC draw stream seed")
+    ap.add_argument("--checkers", action="store_true",
+                    help="RANSAC with the edge-length and distance checkers: 3-point samples, 100000 draws")
     return ap
 
 
@@ -76,7 +79,7 @@ def main(argv=None):
     frags = [read_ply_xyz(f) for f in a.fragments]
     init = None if a.init is None else read_init(a.init, len(frags))
     res = register_scene(frags, a.voxel_size, method=a.icp_method, init=init, dataset=a.dataset, seed=a.seed,
-                         anchor=a.anchor, min_frags=a.min_frags)
+                         anchor=a.anchor, min_frags=a.min_frags, ransac_checkers=a.checkers)
     ensure_dir(a.out)
     write_poses(res["poses"], os.path.join(a.out, "poses.txt"))
     rec = res["pairs"]

@@ -83,6 +83,52 @@ int mvr_ransac(const double* x1, const double* x2, int64_t x_pstride, const int3
                int32_t* best_iter, double* hyp_out, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * RANSAC with correspondence checkers and a validation cap, batched over pairs (csrc/ransac_checked.hip;
+ * DESIGN.md 4.26).  What Open3D's global-registration examples configure (3-point samples,
+ * CorrespondenceCheckerBasedOnEdgeLength(0.9) + ...BasedOnDistance, ...BasedOnNormal, 100000 iterations): a cheap
+ * test per sample decides whether its hypothesis is scored at all.  It replaces nothing in the reference (whose
+ * Open3D 0.9 call passes no checkers: mvr_ransac above, which stays as it is).
+ *   x1, x2, x_pstride, n, P, ransac_n (3..8), iters, max_dist, seed and the draws: as mvr_ransac.
+ *   Iteration `it` of pair p PASSES when, in this order,
+ *     1. edge_sim > 0: no correspondence is drawn twice;
+ *     2. edge_sim > 0: every pair j < k of its draws has ls2 >= sim2 * lt2 and lt2 >= sim2 * ls2, with
+ *        ls2 = (d0*d0 + d1*d1) + d2*d2 of the two source points, lt2 of the two target points and
+ *        sim2 = edge_sim * edge_sim (rounded fp64 operations, no fma, no square root);
+ *     3. the Umeyama fit of its draws, as mvr_ransac computes it;
+ *     4. check_dist > 0: every drawn correspondence has |R s + t - d|^2 < check_dist^2 (the evaluation's own
+ *        operation order);
+ *     5. nrm1 and nrm2 both given: every drawn correspondence has (R n1) . n2 >= normal_cos, each sum left to right.
+ *   edge_sim in [0, 1) (0: checks 1-2 off), check_dist >= 0 (0: off), normal_cos in [-1, 1]; nrm1 / nrm2 fp64 in
+ *   the layout of x1 / x2 (unit normals of the source / target points), either NULL: check 5 off.
+ *   The first max_validation passing iterations, in ascending iteration order, are the validated hypotheses: each
+ *   is scored over all n[p] correspondences as in mvr_ransac, and the result is the best by (inliers descending,
+ *   rmse ascending, iteration ascending).  With every checker off and max_validation >= iters, T, fitness, rmse
+ *   and best_iter equal mvr_ransac's bit for bit.  Nothing depends on scheduling: two runs give the same bytes.
+ *   There is no confidence-based early exit (Open3D >= 0.12 stops once the best fitness makes further draws
+ *   unlikely to improve): when to stop would depend on each pair's running best, which a batched launch of all
+ *   iterations does not have.
+ *   Outputs: T [P,4,4], fitness [P], rmse [P] (identity, 0, 0 when n[p] < ransac_n, nothing passes, or no validated
+ *   hypothesis has an inlier), best_iter [P] (the iteration id; -1: none), n_pass [P] (iterations that pass),
+ *   n_valid [P] = min(n_pass, max_validation).  Optional (NULL: not exported): pass_bits [P][ceil(iters/64)] uint64
+ *   (bit it % 64 of word it / 64), valid_iter [P][max_validation] int32 (the validated iterations, -1 beyond
+ *   n_valid[p]), hyp_out [P][max_validation][12] (R row-major, t of the validated hypotheses; rows beyond
+ *   n_valid[p] are not written).
+ *   workspace (8-byte aligned) >= mvr_ransac_checked_workspace_bytes(P, iters, max_validation): per pair the pass
+ *   bits and, per validated hypothesis, the iteration id, a count, an error sum and 12 doubles.
+ *   MVR_EINVAL: P < 0 or >= 2^23, ransac_n outside 3..8, iters outside (0, 2^30), max_validation < 1, max_dist not
+ *   positive and finite, a non-finite or out-of-range edge_sim / check_dist / normal_cos, P * ceil(iters/256)
+ *   >= 2^31, a short workspace and, with P > 0, a NULL x1, x2, n, T, fitness, rmse, best_iter, n_pass, n_valid or
+ *   workspace.
+ * ---------------------------------------------------------------------- */
+size_t mvr_ransac_checked_workspace_bytes(int P, int iters, int max_validation);
+int mvr_ransac_checked(const double* x1, const double* x2, int64_t x_pstride, const int32_t* n, int P, int ransac_n,
+                       int iters, double max_dist, uint64_t seed, int max_validation, double edge_sim,
+                       double check_dist, const double* nrm1, const double* nrm2, double normal_cos, double* T,
+                       double* fitness, double* rmse, int32_t* best_iter, int32_t* n_pass, int32_t* n_valid,
+                       uint64_t* pass_bits, int32_t* valid_iter, double* hyp_out, void* workspace,
+                       size_t workspace_bytes, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Multiview pose synchronisation, batched over scenes (csrc/sync.hip).
  * The closed-form weighted solve of the paper's sections 3.2-3.3 with optional IRLS; the reference never released
  * this stage (its README.md:116), so it replaces nothing: it turns the pairwise estimates of a scene into one pose

@@ -5,7 +5,9 @@ mvr_feat_match (csrc/feat_match.hip) for the 435 pairs in both directions, and l
 (both matcher launches, the mutual filter and the padding in torch, mvr_ransac), with the share of pairs it registers
 within 15 degrees / 0.3 m of ground truth.  HIP events around each call after a warm-up, median over --reps calls;
 register_fpfh by the host clock around a synchronised call.  --demo also registers tests/golden/demo's pair.
-usage: python tools/fpfh_micro.py [--frags 30] [--reps 5] [--demo]"""
+--checkers repeats the register_fpfh lines with checkers=True (mvr_ransac_checked) and prints how many
+of its 100000 samples per pair passed the checkers and how many were scored.
+usage: python tools/fpfh_micro.py [--frags 30] [--reps 5] [--demo] [--checkers]"""
 import argparse
 import os
 import sys
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--frags", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--demo", action="store_true")
+    ap.add_argument("--checkers", action="store_true")
     a = ap.parse_args()
     frags, poses = synth_scene_fragments(n_frag=a.frags)
     fo = FragmentOverlap(frags, "FCGF", 0.025)
@@ -70,22 +73,29 @@ def main():
     print("mvr_feat_match, %d pairs x 2 directions, C = 33: median %.1f ms (min %.1f, max %.1f); 2 C n_q n_t = %.3g "
           "FLOP -> %.1f TFLOP/s" % (len(pairs), ms[len(ms) // 2], ms[0], ms[-1], flop, flop / ms[len(ms) // 2] * 1e-9),
           flush=True)
-    register_fpfh(fo, pairs[:4])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = register_fpfh(fo, pairs)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    ok = 0
-    for k, (i, j) in enumerate(pairs):
-        Tg = O.gt_transform(poses, i, j)
-        c = frags[i].astype(np.float64).mean(0)
-        D = np.linalg.inv(Tg) @ out["T"][k]
-        ang = np.rad2deg(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
-        ok += ang < 15.0 and np.linalg.norm(D[:3, :3] @ c + D[:3, 3] - c) < 0.3
-    print("register_fpfh, %d pairs end to end: %.1f ms; mutual matches %d..%d (mean %.0f); %d pairs within 15 deg / "
-          "0.3 m of ground truth" % (len(pairs), dt * 1e3, out["n_matches"].min(), out["n_matches"].max(),
-                                     out["n_matches"].mean(), ok), flush=True)
+    for checkers in (False, True)[:1 + a.checkers]:
+        register_fpfh(fo, pairs[:4], checkers=checkers)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = register_fpfh(fo, pairs, checkers=checkers)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        ok = 0
+        for k, (i, j) in enumerate(pairs):
+            Tg = O.gt_transform(poses, i, j)
+            c = frags[i].astype(np.float64).mean(0)
+            D = np.linalg.inv(Tg) @ out["T"][k]
+            ang = np.rad2deg(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
+            ok += ang < 15.0 and np.linalg.norm(D[:3, :3] @ c + D[:3, 3] - c) < 0.3
+        print("register_fpfh%s, %d pairs end to end: %.1f ms; mutual matches %d..%d (mean %.0f); %d pairs within "
+              "15 deg / 0.3 m of ground truth" % ("(checkers=True)" if checkers else "", len(pairs), dt * 1e3,
+                                                  out["n_matches"].min(), out["n_matches"].max(),
+                                                  out["n_matches"].mean(), ok), flush=True)
+        if checkers:
+            print("  samples passing the checkers per pair: %d..%d (median %d, mean %.0f) of 100000; scored: %d..%d "
+                  "(median %d, mean %.0f)" % (out["n_pass"].min(), out["n_pass"].max(), np.median(out["n_pass"]),
+                                             out["n_pass"].mean(), out["n_valid"].min(), out["n_valid"].max(),
+                                             np.median(out["n_valid"]), out["n_valid"].mean()), flush=True)
     if a.demo:
         from lib.ply import read_ply_xyz
         demo = os.path.join(ROOT, "tests", "golden", "demo")
@@ -101,6 +111,15 @@ def main():
         ref = icp_refine(fd, [[0, 1]], r["T"], max_dist=0.05)
         print("  after icp_refine (max_dist 0.05): fitness %.4f, rmse %.4f, %d iterations"
               % (ref["fitness"][0], ref["rmse"][0], ref["iters"][0]))
+        if a.checkers:
+            rc = register_fpfh(fd, [[0, 1]], checkers=True)
+            refc = icp_refine(fd, [[0, 1]], rc["T"], max_dist=0.05)
+            D = np.linalg.inv(r["T"][0]) @ rc["T"][0]
+            print("demo pair, checkers=True: %d of 100000 samples passed, %d scored, RANSAC fitness %.4f, rmse %.4f; "
+                  "after icp_refine fitness %.4f, rmse %.4f; %.2f deg / %.3f m from the plain estimate"
+                  % (rc["n_pass"][0], rc["n_valid"][0], rc["fitness"][0], rc["rmse"][0], refc["fitness"][0],
+                     refc["rmse"][0], np.rad2deg(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1))),
+                     np.linalg.norm(D[:3, 3])))
 
 
 if __name__ == "__main__":
