@@ -4,20 +4,15 @@
 // parameter order (translation, rotation).  Open3D parity and parity with Redwood's published .info files are
 // unpinned (mvreg.h).
 //
-// One workgroup per pair, fp64 throughout.  The correspondences are those of eval(T) in icp.hip; that file is pinned
-// bit for bit by its tests and stays as it is, so the 27-cell walk below is a copy of its search:
-//   search   threads stride over the source points; q = R x + t walks the 27 cells around floor(q / r_index) through
-//            the cell hash, centre cell first; nearest by squared distance, the lowest row on a tie
+// One workgroup per pair, fp64 throughout.  The correspondences are those of an evaluation in the ICP kernels: the
+// same nearest_row of icp_core.hpp finds them.
 //   sums     eleven per thread: n, sum d^2, sum y [3] and the six distinct entries of sum y y^T, about the target
 //            frame's origin (the matrix is defined about it: there is no origin to choose)
 //   reduce   block_sum: a lane tree, then the waves in index order through LDS.  No atomics and no workspace, so a
 //            pair's bits do not depend on the batch around it
 //   assemble lane 0: [ n I, -[sum y]x ; [sum y]x, tr(S) I - S ]
 // Every loop is bounded: the source points, the 27 cells, and the hash probe (cap >= 2 M ends it at an empty slot).
-#include "common.hpp"
-#include "rindex.hpp"
-#include "mvreg.h"
-#include <math.h>
+#include "icp_core.hpp"
 
 namespace mvr {
 
@@ -41,19 +36,10 @@ __global__ __launch_bounds__(kInfoThreads) void info_kernel(InfoArgs a) {
   __shared__ double red[kInfoSums * (kInfoThreads / 64)];
   __shared__ double sT[12];
   const int p = blockIdx.x, tid = threadIdx.x;
-  const int64_t sf = a.pairs[2 * (int64_t)p], tf = a.pairs[2 * (int64_t)p + 1];
   double* out = a.info + 36 * (int64_t)p;
-
   const double* T = a.T + 12 * (int64_t)p;
-  bool ok = sf >= 0 && sf < a.B && tf >= 0 && tf < a.B;
-  for (int q = 0; q < 12; ++q) ok = ok && isfinite(T[q]);
-  int64_t s0 = 0, s1 = 0;
-  if (ok && a.off) {
-    s0 = a.off[sf];
-    s1 = a.off[sf + 1];
-    ok = s0 >= 0 && s0 <= s1 && s1 <= a.M && a.off[tf] >= 0 && a.off[tf + 1] <= a.M;
-  }
-  if (!ok) {   // uniform
+  const PairRange g = pair_range(a.pairs, T, a.off, a.B, a.M, p);
+  if (!g.ok) {   // uniform
     if (tid < 36) out[tid] = 0.0;
     if (tid == 0) {
       a.rmse[p] = 0.0;
@@ -69,38 +55,10 @@ __global__ __launch_bounds__(kInfoThreads) void info_kernel(InfoArgs a) {
   double v[kInfoSums];
 #pragma unroll
   for (int q = 0; q < kInfoSums; ++q) v[q] = 0.0;
-  for (int64_t i = s0 + tid; i < s1; i += kInfoThreads) {
-    const double x = a.xyz[3 * i], y = a.xyz[3 * i + 1], z = a.xyz[3 * i + 2];
-    const double q[3] = {sT[0] * x + sT[1] * y + sT[2] * z + sT[3], sT[4] * x + sT[5] * y + sT[6] * z + sT[7],
-                         sT[8] * x + sT[9] * y + sT[10] * z + sT[11]};
-    int64_t c[3];
-    double lo[3];   // distance to the lower neighbour cell along each axis; r - lo to the upper one
-    for (int e = 0; e < 3; ++e) {
-      const double cf = floor(q[e] / r);
-      c[e] = (int64_t)cf + OV_BIAS;
-      lo[e] = q[e] - cf * r;
-    }
-    double best = md2;
-    int64_t bt = -1;
-    for (int k = 0; k < 27; ++k) {
-      const int cell = (k + 13) % 27;   // the query's own cell first
-      const int dx = cell % 3 - 1, dy = (cell / 3) % 3 - 1, dz = cell / 9 - 1;
-      // a lower bound of the distance to that cell's box: shrunk by a slack far above the rounding of q / r
-      const double gx = dx == 0 ? 0.0 : fmax((dx < 0 ? lo[0] : r - lo[0]) - slack, 0.0);
-      const double gy = dy == 0 ? 0.0 : fmax((dy < 0 ? lo[1] : r - lo[1]) - slack, 0.0);
-      const double gz = dz == 0 ? 0.0 : fmax((dz < 0 ? lo[2] : r - lo[2]) - slack, 0.0);
-      if (gx * gx + gy * gy + gz * gz > best) continue;   // no point of that cell can win
-      const int2 se = cell_find(a.ix, pack_key((int)tf, c[0] + dx, c[1] + dy, c[2] + dz));
-      for (int j = se.x; j < se.y; ++j) {
-        const int64_t t = a.ix.sidx[j];
-        const double ex = q[0] - a.xyz[3 * t], ey = q[1] - a.xyz[3 * t + 1], ez = q[2] - a.xyz[3 * t + 2];
-        const double d2 = ex * ex + ey * ey + ez * ez;
-        if (sqrt(d2) < a.max_dist && (bt < 0 || d2 < best || (d2 == best && t < bt))) {
-          best = d2;
-          bt = t;
-        }
-      }
-    }
+  for (int64_t i = g.s0 + tid; i < g.s1; i += kInfoThreads) {
+    double q[3], best;
+    moved_point(sT, a.xyz, i, q);
+    const int64_t bt = nearest_row(a.ix, a.xyz, g.tf, q, r, slack, md2, a.max_dist, best);
     if (bt >= 0) {
       const double y0 = a.xyz[3 * bt], y1 = a.xyz[3 * bt + 1], y2 = a.xyz[3 * bt + 2];
       v[0] += 1.0;
@@ -136,11 +94,10 @@ extern "C" int mvr_pair_information(const void* index, size_t index_bytes, const
                                     int B, int64_t M, double r_index, const int64_t* pairs, const double* T, int P,
                                     double max_dist, double* info, int32_t* n_corr, double* rmse, int32_t* status,
                                     hipStream_t stream) {
-  if (P < 0 || M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return MVR_EINVAL;
-  if (!(max_dist > 0.0) || !(r_index > 0.0) || max_dist > r_index) return MVR_EINVAL;
+  if (!mvr::search_values_ok(B, M, P, r_index, max_dist)) return MVR_EINVAL;
   if (P == 0) return MVR_OK;   // no pairs: NULL pointers allowed
   if (!pairs || !T || !info || !rmse || !status) return MVR_EINVAL;
-  if (M > 0 && (!index || !xyz || !off || index_bytes < mvr_radius_index_bytes(M))) return MVR_EINVAL;
+  if (!mvr::search_pointers_ok(index, index_bytes, xyz, off, M)) return MVR_EINVAL;
   mvr::InfoArgs a{};
   if (M > 0) a.ix = mvr::index_view(const_cast<void*>(index), M);
   a.xyz = xyz; a.off = M > 0 ? off : nullptr; a.B = B; a.M = M; a.r = r_index;

@@ -1,6 +1,7 @@
 // The per-fragment radius index (built by overlap.hip mvr_radius_index_build): points sorted by (fragment, cell of
-// size r) and an open-addressing hash of the occupied cells.  Shared by the overlap gate (overlap.hip), the ICP
-// refinements (icp.hip, icp_plane.hip) and the normals (normals.hip).  The layout is ABI (mvr_radius_index_bytes).
+// size r) and an open-addressing hash of the occupied cells.  Shared by the overlap gate (overlap.hip), the normals
+// (normals.hip), the FPFH descriptors (fpfh.hip) and, through icp_core.hpp, the ICP refinements (icp.hip,
+// icp_plane.hip, icp_gicp.hip) and the information matrices (info.hip).  The layout is ABI (mvr_radius_index_bytes).
 #pragma once
 #include "common.hpp"
 

@@ -36,6 +36,95 @@ def _check_method(name, method):
         raise ValueError("%s: method must be one of %s, not %r" % (name, ", ".join(METHODS), method))
 
 
+def _check_epsilon(name, epsilon):
+    if not 0.0 < epsilon <= 1.0:
+        raise ValueError("%s: epsilon must lie in (0, 1]" % name)
+
+
+def _run(name, fo, pairs, T_in, T_name, max_dist, needs_normals, call, normals_for=""):
+    """The marshalling every batched entry shares: max_dist against fo.r, T_in [P,4,4] / [P,3,4] and pairs [P,2] to
+    fp64 / int64 on fo's device, fo.normals checked when needs_normals (normals_for: what needs them, for the
+    message), then call(P, pairs, T3) -> dict of device tensors.  The dict comes back on the device when T_in was
+    there, else on the host (numpy for numpy inputs)."""
+    if max_dist > fo.r:
+        raise ValueError("%s: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
+                         "radius >= max_dist)" % (name, max_dist, fo.r))
+    was_numpy = not torch.is_tensor(T_in)
+    Tin = torch.as_tensor(T_in)
+    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("%s: %s must be a float [P,4,4] or [P,3,4]" % (name, T_name))
+    ij = torch.as_tensor(pairs)
+    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
+        raise ValueError("%s: pairs must be [P,2] with one row per transform" % name)
+    if needs_normals:
+        nrm = getattr(fo, "normals", None)
+        if nrm is None:
+            raise ValueError("%s: %sneeds fo.normals (call fo.estimate_normals())" % (name, normals_for))
+        if not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64 or \
+                nrm.device != fo.xyz.device or not nrm.is_contiguous():
+            raise ValueError("%s: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
+                             % (name, fo.M))
+    N.require_hip()
+    out = call(int(Tin.shape[0]), ij.to(fo.device, torch.int64).contiguous(),
+               Tin[:, :3, :].to(fo.device, torch.float64).contiguous())
+    if Tin.device.type != "cuda":
+        out = {k: v.cpu() for k, v in out.items()}
+        if was_numpy:
+            out = {k: v.numpy() for k, v in out.items()}
+    return out
+
+
+def _refine(name, fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace, entry, needs_normals,
+            normals_for="", epsilon=None):
+    """icp_refine and gicp_refine after their own checks: entry names the C function, which takes the normals when
+    needs_normals and epsilon when that is not None."""
+    def call(P, ij, T0):
+        dev = fo.device
+        T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
+        fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
+        n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+        trace = torch.empty(P, int(max_iters) + 1, 2, dtype=torch.float64, device=dev) if return_trace else None
+        head = (N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz)) + \
+            ((N.ptr(fo.normals),) if needs_normals else ()) + (N.ptr(fo.off_dev), fo.B, fo.M)
+        eps = () if epsilon is None else (float(epsilon),)
+        N.check(getattr(N.lib(), entry)(*head, fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, *eps, int(max_iters),
+                                        float(tol_fitness), float(tol_rmse), N.ptr(T), N.ptr(fitness), N.ptr(rmse),
+                                        N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream()), entry)
+        T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
+        T4[:, :3], T4[:, 3, 3] = T, 1.0
+        out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
+        if return_trace:
+            out["trace"] = trace
+        return out
+    return _run(name, fo, pairs, T_init, "T_init", max_dist, needs_normals, call, normals_for)
+
+
+def _pair_overlap(name, src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, normals):
+    """The shape checks of icp_pair and gicp_pair, then the two-fragment FragmentOverlap (with normals over
+    normal_radius, None: max_dist, if asked for) and T_init with the leading [1]."""
+    from lib.overlap import FragmentOverlap
+    if normal_radius is not None and not normal_radius > 0.0:
+        raise ValueError("%s: normal_radius must be positive" % name)
+    if voxel_size is not None and not voxel_size > 0.0:
+        raise ValueError("%s: voxel_size must be positive" % name)
+    for what, x in (("src_xyz", src_xyz), ("tgt_xyz", tgt_xyz)):
+        shape = tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError("%s: %s must be [n,3]" % (name, what))
+    Tin = torch.as_tensor(T_init)
+    if tuple(Tin.shape) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
+        raise ValueError("%s: T_init must be a float [4,4] or [3,4]" % name)
+    nr = max_dist if normal_radius is None else normal_radius
+    cell = max(max_dist, nr) if normals else max_dist    # the index's cells cover the search ball and the normals'
+    if voxel_size is None:
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell)
+    else:
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell)
+    if normals:
+        fo.estimate_normals(nr)
+    return fo, (T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None])
+
+
 def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, return_trace=False,
                method="point_to_point"):
     """Refine the transform of every pair on the points of `fo` (a lib.overlap.FragmentOverlap: its centroids for
@@ -53,53 +142,9 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     max_dist = float(fo.r if max_dist is None else max_dist)
     _check_settings("icp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
     _check_method("icp_refine", method)
-    if max_dist > fo.r:
-        raise ValueError("icp_refine: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
-                         "radius >= max_dist)" % (max_dist, fo.r))
-    was_numpy = not torch.is_tensor(T_init)
-    Tin = torch.as_tensor(T_init)
-    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
-        raise ValueError("icp_refine: T_init must be a float [P,4,4] or [P,3,4]")
-    ij = torch.as_tensor(pairs)
-    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
-        raise ValueError("icp_refine: pairs must be [P,2] with one row per transform")
     plane = method == "point_to_plane"
-    if plane:
-        nrm = getattr(fo, "normals", None)
-        if nrm is None:
-            raise ValueError("icp_refine: method 'point_to_plane' needs fo.normals (call fo.estimate_normals())")
-        if not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64 or \
-                nrm.device != fo.xyz.device or not nrm.is_contiguous():
-            raise ValueError("icp_refine: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
-                             % fo.M)
-    N.require_hip()
-    on_dev = Tin.device.type == "cuda"
-    dev = fo.device
-    P, rows = int(Tin.shape[0]), int(max_iters) + 1
-    T0 = Tin[:, :3, :].to(dev, torch.float64).contiguous()
-    ij = ij.to(dev, torch.int64).contiguous()
-    T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
-    fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
-    n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
-    trace = torch.empty(P, rows, 2, dtype=torch.float64, device=dev) if return_trace else None
-    tail = (fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, int(max_iters), float(tol_fitness), float(tol_rmse), N.ptr(T),
-            N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream())
-    if plane:
-        N.check(N.lib().mvr_icp_refine_plane(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals),
-                                             N.ptr(fo.off_dev), fo.B, fo.M, *tail), "mvr_icp_refine_plane")
-    else:
-        N.check(N.lib().mvr_icp_refine(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
-                                       fo.M, *tail), "mvr_icp_refine")
-    T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
-    T4[:, :3], T4[:, 3, 3] = T, 1.0
-    out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
-    if return_trace:
-        out["trace"] = trace
-    if not on_dev:
-        out = {k: v.cpu() for k, v in out.items()}
-        if was_numpy:
-            out = {k: v.numpy() for k, v in out.items()}
-    return out
+    return _refine("icp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
+                   "mvr_icp_refine_plane" if plane else "mvr_icp_refine", plane, "method 'point_to_plane' ")
 
 
 INFO_ORDERS = ("redwood", "open3d")
@@ -135,34 +180,17 @@ def information_matrix(fo, pairs, T, max_dist=None, order="redwood"):
         raise ValueError("information_matrix: max_dist must be positive")
     if order not in INFO_ORDERS:
         raise ValueError("information_matrix: order must be one of %s, not %r" % (", ".join(INFO_ORDERS), order))
-    if max_dist > fo.r:
-        raise ValueError("information_matrix: max_dist %g exceeds the index's cell size %g (build the "
-                         "FragmentOverlap with radius >= max_dist)" % (max_dist, fo.r))
-    was_numpy = not torch.is_tensor(T)
-    Tin = torch.as_tensor(T)
-    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
-        raise ValueError("information_matrix: T must be a float [P,4,4] or [P,3,4]")
-    ij = torch.as_tensor(pairs)
-    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
-        raise ValueError("information_matrix: pairs must be [P,2] with one row per transform")
-    N.require_hip()
-    on_dev = Tin.device.type == "cuda"
-    dev = fo.device
-    P = int(Tin.shape[0])
-    T3 = Tin[:, :3, :].to(dev, torch.float64).contiguous()
-    ij = ij.to(dev, torch.int64).contiguous()
-    info = torch.empty(P, 36, dtype=torch.float64, device=dev)
-    rmse = torch.empty(P, dtype=torch.float64, device=dev)
-    n_corr, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(2))
-    N.check(N.lib().mvr_pair_information(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
-                                         fo.M, fo.r, N.ptr(ij), N.ptr(T3), P, max_dist, N.ptr(info), N.ptr(n_corr),
-                                         N.ptr(rmse), N.ptr(status), N.stream()), "mvr_pair_information")
-    out = {"info": permute_information(info.view(P, 6, 6), order), "n_corr": n_corr, "rmse": rmse, "status": status}
-    if not on_dev:
-        out = {k: v.cpu() for k, v in out.items()}
-        if was_numpy:
-            out = {k: v.numpy() for k, v in out.items()}
-    return out
+
+    def call(P, ij, T3):
+        info = torch.empty(P, 36, dtype=torch.float64, device=fo.device)
+        rmse = torch.empty(P, dtype=torch.float64, device=fo.device)
+        n_corr, status = (torch.empty(P, dtype=torch.int32, device=fo.device) for _ in range(2))
+        N.check(N.lib().mvr_pair_information(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
+                                             fo.M, fo.r, N.ptr(ij), N.ptr(T3), P, max_dist, N.ptr(info), N.ptr(n_corr),
+                                             N.ptr(rmse), N.ptr(status), N.stream()), "mvr_pair_information")
+        return {"info": permute_information(info.view(P, 6, 6), order), "n_corr": n_corr, "rmse": rmse,
+                "status": status}
+    return _run("information_matrix", fo, pairs, T, "T", max_dist, False, call)
 
 
 def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="point_to_point", normal_radius=None,
@@ -173,38 +201,13 @@ def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="p
     return_trace of icp_refine.  method 'point_to_plane': the normals are estimated here over normal_radius (None:
     max_dist) on an index of cell max(max_dist, normal_radius); TransformationEstimationPointToPlane after
     estimate_normals(KDTreeSearchParamRadius(normal_radius)).  Returns icp_refine's dict without the leading [P]."""
-    from lib.overlap import FragmentOverlap
     _check_settings("icp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
                     kw.get("tol_rmse", 0.0))
     _check_method("icp_pair", method)
-    if normal_radius is not None and not normal_radius > 0.0:
-        raise ValueError("icp_pair: normal_radius must be positive")
-    if voxel_size is not None and not voxel_size > 0.0:
-        raise ValueError("icp_pair: voxel_size must be positive")
-    for name, x in (("src_xyz", src_xyz), ("tgt_xyz", tgt_xyz)):
-        shape = tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
-        if len(shape) != 2 or shape[1] != 3:
-            raise ValueError("icp_pair: %s must be [n,3]" % name)
-    Tin = torch.as_tensor(T_init)
-    if tuple(Tin.shape) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
-        raise ValueError("icp_pair: T_init must be a float [4,4] or [3,4]")
-    plane = method == "point_to_plane"
-    nr = max_dist if normal_radius is None else normal_radius
-    cell = max(max_dist, nr) if plane else max_dist      # the index's cells cover the search ball and the normals'
-    if voxel_size is None:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell)
-    else:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell)
-    if plane:
-        fo.estimate_normals(nr)
-    T0 = T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None]
+    fo, T0 = _pair_overlap("icp_pair", src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius,
+                           method == "point_to_plane")
     out = icp_refine(fo, [[0, 1]], T0, max_dist, method=method, **kw)
     return {k: v[0] for k, v in out.items()}
-
-
-def _check_epsilon(name, epsilon):
-    if not 0.0 < epsilon <= 1.0:
-        raise ValueError("%s: epsilon must lie in (0, 1]" % name)
 
 
 def gicp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, epsilon=1e-3,
@@ -219,48 +222,8 @@ def gicp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6
     max_dist = float(fo.r if max_dist is None else max_dist)
     _check_settings("gicp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
     _check_epsilon("gicp_refine", epsilon)
-    if max_dist > fo.r:
-        raise ValueError("gicp_refine: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
-                         "radius >= max_dist)" % (max_dist, fo.r))
-    was_numpy = not torch.is_tensor(T_init)
-    Tin = torch.as_tensor(T_init)
-    if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
-        raise ValueError("gicp_refine: T_init must be a float [P,4,4] or [P,3,4]")
-    ij = torch.as_tensor(pairs)
-    if ij.dim() != 2 or ij.shape[1] != 2 or ij.shape[0] != Tin.shape[0]:
-        raise ValueError("gicp_refine: pairs must be [P,2] with one row per transform")
-    nrm = getattr(fo, "normals", None)
-    if nrm is None:
-        raise ValueError("gicp_refine: needs fo.normals (call fo.estimate_normals())")
-    if not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64 or \
-            nrm.device != fo.xyz.device or not nrm.is_contiguous():
-        raise ValueError("gicp_refine: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
-                         % fo.M)
-    N.require_hip()
-    on_dev = Tin.device.type == "cuda"
-    dev = fo.device
-    P, rows = int(Tin.shape[0]), int(max_iters) + 1
-    T0 = Tin[:, :3, :].to(dev, torch.float64).contiguous()
-    ij = ij.to(dev, torch.int64).contiguous()
-    T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
-    fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
-    n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
-    trace = torch.empty(P, rows, 2, dtype=torch.float64, device=dev) if return_trace else None
-    N.check(N.lib().mvr_icp_refine_generalized(
-        N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals), N.ptr(fo.off_dev), fo.B, fo.M, fo.r,
-        N.ptr(ij), N.ptr(T0), P, max_dist, float(epsilon), int(max_iters), float(tol_fitness), float(tol_rmse),
-        N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream()),
-        "mvr_icp_refine_generalized")
-    T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
-    T4[:, :3], T4[:, 3, 3] = T, 1.0
-    out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
-    if return_trace:
-        out["trace"] = trace
-    if not on_dev:
-        out = {k: v.cpu() for k, v in out.items()}
-        if was_numpy:
-            out = {k: v.numpy() for k, v in out.items()}
-    return out
+    return _refine("gicp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
+                   "mvr_icp_refine_generalized", True, epsilon=epsilon)
 
 
 def gicp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, normal_radius=None, epsilon=1e-3, **kw):
@@ -268,28 +231,9 @@ def gicp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, normal_r
     init): icp_pair's arguments.  The normals of both clouds are estimated here over normal_radius (None: max_dist) on
     an index of cell max(max_dist, normal_radius).  **kw: max_iters, tol_fitness, tol_rmse, return_trace of
     gicp_refine.  Returns gicp_refine's dict without the leading [P]."""
-    from lib.overlap import FragmentOverlap
     _check_settings("gicp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
                     kw.get("tol_rmse", 0.0))
     _check_epsilon("gicp_pair", epsilon)
-    if normal_radius is not None and not normal_radius > 0.0:
-        raise ValueError("gicp_pair: normal_radius must be positive")
-    if voxel_size is not None and not voxel_size > 0.0:
-        raise ValueError("gicp_pair: voxel_size must be positive")
-    for name, x in (("src_xyz", src_xyz), ("tgt_xyz", tgt_xyz)):
-        shape = tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
-        if len(shape) != 2 or shape[1] != 3:
-            raise ValueError("gicp_pair: %s must be [n,3]" % name)
-    Tin = torch.as_tensor(T_init)
-    if tuple(Tin.shape) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
-        raise ValueError("gicp_pair: T_init must be a float [4,4] or [3,4]")
-    nr = max_dist if normal_radius is None else normal_radius
-    cell = max(max_dist, nr)                             # the index's cells cover the search ball and the normals'
-    if voxel_size is None:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell)
-    else:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell)
-    fo.estimate_normals(nr)
-    T0 = T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None]
+    fo, T0 = _pair_overlap("gicp_pair", src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, True)
     out = gicp_refine(fo, [[0, 1]], T0, max_dist, epsilon=epsilon, **kw)
     return {k: v[0] for k, v in out.items()}

@@ -227,6 +227,17 @@ def small_normals_case(seed=4):
     return frags
 
 
+def small_normals_pairs(seed=6):
+    """Pairs and starts on small_normals_case for the searches that share one core: every fragment as the source
+    against the 1025-point cloud (itself included) and that cloud against every other fragment, each from the identity
+    perturbed by 1.5 degrees and sigma 4 mm, so that no distance is zero.  -> (pairs [15,2], T0 [15,4,4])"""
+    rng = np.random.default_rng(seed)
+    big = len(SMALL_SIZES) - 1
+    pairs = [(s, big) for s in range(big + 1)] + [(big, t) for t in range(big)]
+    T0 = [O.perturb(np.eye(4), np.zeros(3), rng, 1.5, 0.004) for _ in pairs]
+    return np.asarray(pairs), np.asarray(T0)
+
+
 CORNER_RADIUS = 0.1                    # cell, normal radius and max_dist of corner_case
 
 

@@ -202,6 +202,33 @@ def test_invalid_pairs(gpu):
         assert alone[name].tobytes() == got[name][ok].tobytes(), name
 
 
+def test_four_entries_share_one_search(gpu):
+    """One evaluation (max_iters 0) of small_normals_case's fragments of 0, 1, 2, 3, 63, 64, 65 and 1025 points: the
+    three refinements and information_matrix count the same correspondences, and their rmse (and the refinements'
+    fitness) is the same bit for bit.  The per-thread summands of n and sum d^2 are the same in the same order, and
+    block_sum reduces each component independently of how many there are."""
+    from lib.icp import gicp_refine, icp_refine, information_matrix
+    from lib.overlap import FragmentOverlap
+    fo = FragmentOverlap(PO.small_normals_case(), "3DMatch", radius=PO.SMALL_R_INDEX)
+    fo.estimate_normals()
+    pairs, T0 = PO.small_normals_pairs()
+    kw = dict(max_iters=0, tol_fitness=0.0, tol_rmse=0.0)
+    got = [icp_refine(fo, pairs, T0, method=m, **kw) for m in ("point_to_point", "point_to_plane")] + \
+        [gicp_refine(fo, pairs, T0, **kw), information_matrix(fo, pairs, T0)]
+    ref = got[0]
+    print("n_corr %s\nrmse %s" % (ref["n_corr"].tolist(), ref["rmse"].tolist()))
+    assert (ref["status"] == 0).all() and (ref["iters"] == 0).all()
+    big = len(PO.SMALL_SIZES) - 1                # sources 0..big against the cloud, then the cloud against targets 0..
+    assert ref["n_corr"][big] == 1025 and ref["n_corr"][0] == 0 and ref["n_corr"][big + 1] == 0
+    assert (ref["n_corr"][1:big] == PO.SMALL_SIZES[1:big]).all() and (ref["n_corr"][big + 2:] > 0).all()
+    assert ((ref["rmse"] > 0) == (ref["n_corr"] > 0)).all()
+    for other in got[1:]:
+        np.testing.assert_array_equal(other["n_corr"], ref["n_corr"])
+        assert other["rmse"].tobytes() == ref["rmse"].tobytes()
+        if "fitness" in other:
+            assert other["fitness"].tobytes() == ref["fitness"].tobytes()
+
+
 # -------------------------------------------------------------------------------------------------------- invariances
 def test_outputs_do_not_depend_on_the_batch(gpu):
     from lib.icp import gicp_refine

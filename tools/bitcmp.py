@@ -1,7 +1,9 @@
 """Bit-identity check between two builds of libmvreg_hip.so (tools' A/B variants, MVR_LIB).
   python tools/bitcmp.py dump <out.npz>      run the strict train-mode OANet fixture (32 pairs x 5000, both blocks:
-                                             logits, scores, R, t) and one scene step of the bench workload (records
-                                             of all 435 pairs), save them
+                                             logits, scores, R, t), one scene step of the bench workload (records
+                                             of all 435 pairs) and the radius-index refinements (the three ICP
+                                             methods and mvr_pair_information on the tests' scene and small shapes:
+                                             every output), save them
   python tools/bitcmp.py cmp <a.npz> <b.npz> count the elements that differ bit for bit (exit 1 if any)"""
 import os
 import sys
@@ -9,7 +11,40 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+for p in (ROOT, os.path.join(ROOT, "3d_multiview_reg_amd"), os.path.join(ROOT, "tests"),
+          os.path.join(ROOT, "tests", "golden")):
+    sys.path.insert(0, p)
+
+
+def refinements():
+    """every output of icp_refine (both methods), gicp_refine and information_matrix: the 4-fragment scene's six pairs
+    over 30 iterations at tolerances 0, and the tests' small shapes"""
+    import icp_oracle as O
+    import icp_plane_oracle as PO
+    import info_oracle as IO
+    from lib.icp import gicp_refine, icp_refine, information_matrix
+    from lib.overlap import FragmentOverlap
+    kw = dict(max_iters=30, tol_fitness=0.0, tol_rmse=0.0, return_trace=True)
+    runs = {"p2p": lambda *a: icp_refine(*a, **kw), "p2l": lambda *a: icp_refine(*a, method="point_to_plane", **kw),
+            "gicp": lambda *a: gicp_refine(*a, **kw), "info": information_matrix}
+    res = {}
+
+    def add(case, fo, pairs, T0, max_dist, which):
+        for name in which:
+            for k, v in runs[name](fo, pairs, T0, max_dist).items():
+                res["%s_%s_%s" % (case, name, k)] = v
+
+    fo = FragmentOverlap(O.scene4()[0], "FCGF", 0.025)
+    fo.estimate_normals()
+    add("six", fo, O.SIX, O.scene4_starts(O.SIX, O.scene4_centroids()), 0.075, runs)
+    frags, pairs, T0 = O.small_case()
+    add("small", FragmentOverlap(frags, "3DMatch", radius=O.SMALL_RADIUS), pairs, T0, O.SMALL_MAX_DIST, ["p2p"])
+    fo = FragmentOverlap(PO.small_normals_case(), "3DMatch", radius=PO.SMALL_R_INDEX)
+    fo.estimate_normals()
+    add("smalln", fo, *PO.small_normals_pairs(), PO.SMALL_R_INDEX, runs)
+    _, frags, pairs, T, max_dist = [c for c in IO.cases() if c[0] == "small"][0]
+    add("smallinfo", FragmentOverlap(list(frags), "3DMatch", radius=O.SMALL_RADIUS), pairs, T, max_dist, ["info"])
+    return res
 
 
 def dump(path):
@@ -29,6 +64,7 @@ def dump(path):
     wl = bench.SceneWorkload(dev, 0)
     with torch.no_grad():
         res["scene_records"] = wl.step().cpu().numpy()
+    res.update(refinements())
     np.savez(path, **res)
     print("dumped", path, {k: v.shape for k, v in res.items()})
 

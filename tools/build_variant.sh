@@ -11,7 +11,8 @@ make -s -C "$C" >/dev/null
 base=$(basename "$SRC" .hip)
 HASH=$(cd "$C" && cat $(ls *.hip *.hpp | sort) ../../include/mvreg.h | sha256sum | cut -c1-16)
 FL="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -I$R/include -Wall -Wno-unused-function"
-$FL "$@" -c "$C/$SRC" -o "$R/tools/vsp/obj/$NAME.o"
+PERFILE=$(make -s -C "$C" --eval="perfile: ; @echo \$(FLAGS_$base)" perfile)   # the Makefile's flags for that source
+$FL $PERFILE "$@" -c "$C/$SRC" -o "$R/tools/vsp/obj/$NAME.o"
 $FL -DMVR_SRC_HASH="\"$HASH+$NAME:$*\"" -c "$C/prof.hip" -o "$R/tools/vsp/obj/${NAME}_prof.o"
 objs=$(ls "$C"/build/*.o | grep -v "/$base.o" | grep -v "/prof.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$R/tools/vsp/$NAME.so" $objs "$R/tools/vsp/obj/$NAME.o" \
