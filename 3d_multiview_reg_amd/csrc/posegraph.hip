@@ -2,7 +2,8 @@
 // mvr_posegraph_optimize): the last stage of Open3D's multiway registration (global_optimization,
 // Levenberg-Marquardt) and of Choi et al. 2015, restated from the maths; tests/posegraph_oracle.py is the normative
 // text.  Minimises  c = sum_k w_k xi_k^T L_k xi_k,  xi_k = (v, omega) of D_k = M_j^-1 M_i T_k^-1,  from the poses
-// mvr_sync_poses (or anything else) gives, with the anchor held.
+// mvr_sync_poses (or anything else) gives, with the anchor held.  mvr_posegraph_optimize_lp (DESIGN.md 4.22a;
+// tests/posegraph_lp_oracle.py) is the same kernel with a line process on the uncertain edges.
 //
 // One 512-thread workgroup per scene, every trial inside the one launch, fp64 throughout, no floating-point or
 // global atomics (two flag words in LDS are set by atomicOr: idempotent, so order cannot show).  Per trial:
@@ -23,6 +24,7 @@
 #include "common.hpp"
 #include "mvreg.h"
 #include <math.h>
+#include <type_traits>
 
 namespace mvr {
 
@@ -40,6 +42,12 @@ struct PgArgs {
   double* R; double* t; int64_t fs;
   int32_t* member; double* cost; int32_t* iters; int32_t* status; double* trace;
   double* ws; int64_t ws_stride;   // doubles per scene: w [max_edges], B b [42 max_edges], matrix [(6F + 1) 6F]
+};
+
+// mvr_posegraph_optimize_lp's: the workspace then ends with l [max_edges] and r [max_edges] per scene
+struct PgLpArgs : PgArgs {
+  const int32_t* unc; double mu_scale;
+  double* line; double* mu;
 };
 
 // omega = log(R) as a rotation vector: a = vee(R - R^T) / 2 has |a| = sin(theta), (tr R - 1) / 2 = cos(theta)
@@ -127,7 +135,15 @@ __device__ static bool chol6(const double* A, int n, double (&L)[21]) {
   return ok;
 }
 
-__global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
+// kLineProcess (mvr_posegraph_optimize_lp; tests/posegraph_lp_oracle.py): the counted uncertain edges carry a weight
+// l_k = (mu / (mu + r_k))^2, r_k = w_k xi_k^T L_k xi_k, held through a trial and recomputed in closed form after an
+// accepted one from the r_k the candidate's cost pass left in the workspace.  Thread e % 512 owns edge e in every
+// per-edge pass, so l and r need no barrier of their own.  The held cost is (sum_certain r + sum_uncertain l r) + pen,
+// pen = mu sum_uncertain (s - 1)^2: without an uncertain edge the last two are 0.0 and the first is the plain
+// kernel's sum, term for term
+template <bool kLineProcess>
+__global__ __launch_bounds__(kPgThreads) void posegraph_kernel(
+    std::conditional_t<kLineProcess, PgLpArgs, PgArgs> a) {
   __shared__ double sP[6][kPgN + 1];            // the factor's current panel, by column
   __shared__ double sD[kPgN];                   // delta
   __shared__ double sR[kPgF][9], sT[kPgF][3];   // the poses
@@ -155,6 +171,8 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
   double* wc = a.ws + (int64_t)s * a.ws_stride;   // the weight that counts: 0 for an ignored edge
   double* Bb = wc + a.max_edges;                  // per edge B [36], b [6]
   double* M = Bb + 42 * (int64_t)a.max_edges;
+  double* lw = M + (6 * (int64_t)a.max_frags + 1) * 6 * (int64_t)a.max_frags;   // kLineProcess: l per edge
+  double* rk = lw + a.max_edges;                                               // kLineProcess: r per uncertain edge
 
   // ---- an invalid scene: poses copied through
   if (tid == 0) sFlag[0] = 0;
@@ -179,6 +197,10 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
     }
     if (trace)
       for (int64_t e = tid; e < rows; e += kPgThreads) trace[e] = -1.0;
+    if constexpr (kLineProcess) {
+      for (int e = tid; e < min(max(E, 0), a.max_edges); e += kPgThreads) a.line[(int64_t)s * a.es + e] = 0.0;
+      if (tid == 0 && a.mu) a.mu[s] = 0.0;
+    }
     if (tid == 0) {
       a.cost[2 * s] = 0.0;
       a.cost[2 * s + 1] = 0.0;
@@ -259,7 +281,75 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
     return acc[0];
   };
 
-  double c = cost_of(sR, sT);
+  // ---- the line process: mu, then l in closed form at the initial poses
+  double mu = 0.0, pen = 0.0;
+  bool lp_on = false;
+  const int32_t* unc = nullptr;
+  if constexpr (kLineProcess) {
+    unc = a.unc ? a.unc + (int64_t)s * a.es : nullptr;
+    double acc[2] = {0.0, 0.0};
+    for (int e = tid; e < E; e += kPgThreads) {
+      lw[e] = 1.0;
+      if (wc[e] > 0.0 && (!unc || unc[e] != 0)) {
+        acc[0] += info[(int64_t)36 * e];
+        acc[1] += 1.0;
+      }
+    }
+    block_sum<2>(acc, red);
+    if (acc[1] > 0.0) {
+      mu = a.mu_scale * (acc[0] / acc[1]);
+      lp_on = mu > 0.0 && isfinite(mu);
+      if (!lp_on) status |= 16;
+    }
+  }
+  // (sum over the certain edges of r, over the uncertain ones of l r with the l held) at the poses (PR, PT), in every
+  // thread; r of every uncertain edge is left in rk
+  auto cost_lp = [&](const double (*PR)[9], const double (*PT)[3], double (&acc)[2]) {
+    acc[0] = 0.0;
+    acc[1] = 0.0;
+    for (int e = tid; e < E; e += kPgThreads) {
+      const double wgt = wc[e];
+      if (wgt > 0.0) {
+        const int i = ij[2 * e], j = ij[2 * e + 1];
+        double xi[6], L[36];
+        pg_residual(PR[i], PT[i], PR[j], PT[j], Rp + (int64_t)9 * e, tp + (int64_t)3 * e, xi);
+        pg_lambda(info + (int64_t)36 * e, L);
+        const double q = pg_quad(L, xi);
+        if (lp_on && (!unc || unc[e] != 0)) {
+          const double r = wgt * q;
+          rk[e] = r;
+          acc[1] += lw[e] * r;
+        } else {
+          acc[0] += wgt * q;
+        }
+      }
+    }
+    block_sum<2>(acc, red);
+  };
+  // l <- (mu / (mu + r))^2 from rk; -> (sum_uncertain l r, sum_uncertain (s - 1)^2) in every thread
+  auto lp_update = [&](double (&acc)[2]) {
+    acc[0] = 0.0;
+    acc[1] = 0.0;
+    for (int e = tid; e < E; e += kPgThreads)
+      if (wc[e] > 0.0 && (!unc || unc[e] != 0)) {
+        const double r = rk[e], sk = mu / (mu + r), l = sk * sk;
+        lw[e] = l;
+        acc[0] += l * r;
+        acc[1] += (sk - 1.0) * (sk - 1.0);
+      }
+    block_sum<2>(acc, red);
+  };
+
+  double c;
+  if constexpr (kLineProcess) {
+    double sums[2], upd[2] = {0.0, 0.0};
+    cost_lp(sR, sT, sums);       // l is 1 still: the second sum is formed and dropped
+    if (lp_on) lp_update(upd);   // uniform
+    pen = mu * upd[1];
+    c = (sums[0] + upd[0]) + pen;
+  } else {
+    c = cost_of(sR, sT);
+  }
   const double c_init = c;
   if (trace && tid == 0) trace[0] = c;
   double lam = a.lambda0;
@@ -272,6 +362,8 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
       for (int e = tid; e < E; e += kPgThreads) {
         const double wgt = wc[e];
         if (!(wgt > 0.0)) continue;
+        double wl = wgt;
+        if constexpr (kLineProcess) wl = wgt * lw[e];
         const int i = ij[2 * e], j = ij[2 * e + 1];
         const double* Rj = sR[j];
         const double* tj = sT[j];
@@ -305,11 +397,11 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
           for (int r = 0; r < 6; ++r) {
             double acc = 0.0;
             for (int q = 0; q < 6; ++q) acc += A[6 * q + r] * u[q];
-            out[6 * r + cc] = wgt * acc;
+            out[6 * r + cc] = wl * acc;
           }
           double acc = 0.0;
           for (int q = 0; q < 6; ++q) acc += A[6 * q + cc] * Lx[q];
-          out[36 + cc] = wgt * acc;
+          out[36 + cc] = wl * acc;
         }
       }
     __syncthreads();
@@ -432,12 +524,26 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
         for (int q = 0; q < 6; ++q) mx = fmax(mx, fabs(d[q]));
       }
       step = block_max(mx, red);   // its barriers also order the candidate's writes before the reads below
-      cn = cost_of(cR, cT);
+      double sums[2];
+      if constexpr (kLineProcess) {
+        cost_lp(cR, cT, sums);
+        cn = (sums[0] + sums[1]) + pen;
+      } else {
+        cn = cost_of(cR, cT);
+      }
       accepted = cn < c;
       if (accepted) {
         for (int e = tid; e < 12 * N; e += kPgThreads) {
           const int f = e / 12, q = e % 12;
           if (q < 9) sR[f][q] = cR[f][q]; else sT[f][q - 9] = cT[f][q - 9];
+        }
+        if constexpr (kLineProcess) {
+          if (lp_on) {   // uniform: l in closed form at the accepted poses, c'' <= c'
+            double upd[2];
+            lp_update(upd);
+            pen = mu * upd[1];
+            cn = (sums[0] + upd[0]) + pen;
+          }
         }
         if (c - cn <= a.tol_cost * c) converged = true;
         c = cn;
@@ -462,6 +568,10 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(PgArgs a) {
   }
   if (trace)
     for (int64_t e = (int64_t)k + 1 + tid; e < rows; e += kPgThreads) trace[e] = -1.0;
+  if constexpr (kLineProcess) {
+    for (int e = tid; e < E; e += kPgThreads) a.line[(int64_t)s * a.es + e] = wc[e] > 0.0 ? lw[e] : 0.0;
+    if (tid == 0 && a.mu) a.mu[s] = mu;
+  }
   if (tid == 0) {
     a.cost[2 * s] = c_init;
     a.cost[2 * s + 1] = c;
@@ -477,13 +587,19 @@ extern "C" size_t mvr_posegraph_workspace_bytes(int S, int max_frags, int max_ed
   return (size_t)S * (43 * (size_t)max_edges + (6 * (size_t)max_frags + 1) * 6 * (size_t)max_frags) * sizeof(double);
 }
 
-extern "C" int mvr_posegraph_optimize(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w,
-                                      const double* info, int64_t e_sstride, const int32_t* n_edges,
-                                      const int32_t* n_frags, int S, int max_frags, int max_edges, int anchor,
-                                      const double* R0, const double* t0, int max_iters, double lambda0,
-                                      double tol_cost, double tol_step, double* R, double* t, int64_t f_sstride,
-                                      int32_t* member, double* cost, int32_t* iters, int32_t* status, double* trace,
-                                      void* workspace, size_t workspace_bytes, hipStream_t stream) {
+extern "C" size_t mvr_posegraph_lp_workspace_bytes(int S, int max_frags, int max_edges) {
+  if (S <= 0 || max_frags < 0 || max_edges < 0) return 0;
+  return mvr_posegraph_workspace_bytes(S, max_frags, max_edges) + (size_t)S * 2 * (size_t)max_edges * sizeof(double);
+}
+
+// the argument rules both entries share, then the arguments; -> MVR_OK with *launch false when there is nothing to do
+static int pg_arguments(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w,
+                        const double* info, int64_t e_sstride, const int32_t* n_edges, const int32_t* n_frags, int S,
+                        int max_frags, int max_edges, int anchor, const double* R0, const double* t0, int max_iters,
+                        double lambda0, double tol_cost, double tol_step, double* R, double* t, int64_t f_sstride,
+                        int32_t* member, double* cost, int32_t* iters, int32_t* status, double* trace, void* workspace,
+                        size_t workspace_bytes, size_t need, int64_t extra, mvr::PgArgs& a, bool* launch) {
+  *launch = false;
   if (S < 0 || max_frags < 0 || max_edges < 0 || max_iters < 0 || max_frags > MVR_SYNC_MAX_FRAGS || anchor < 0 ||
       (max_frags > 0 && anchor >= max_frags))
     return MVR_EINVAL;
@@ -492,10 +608,7 @@ extern "C" int mvr_posegraph_optimize(const double* R_pair, const double* t_pair
   if (!n_edges || !n_frags || !status || !cost || !iters || !R || !t || !R0 || !t0) return MVR_EINVAL;
   if (max_edges > 0 && (!R_pair || !t_pair || !ij || !info)) return MVR_EINVAL;
   if (S > 1 && (e_sstride < max_edges || f_sstride < max_frags)) return MVR_EINVAL;
-  if (!workspace || workspace_bytes < mvr_posegraph_workspace_bytes(S, max_frags, max_edges) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 7))
-    return MVR_EINVAL;
-  mvr::PgArgs a{};
+  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7)) return MVR_EINVAL;
   a.Rp = R_pair; a.tp = t_pair; a.ij = ij; a.w = w; a.info = info; a.es = e_sstride;
   a.n_edges = n_edges; a.n_frags = n_frags;
   a.max_frags = max_frags; a.max_edges = max_edges; a.anchor = anchor;
@@ -504,8 +617,49 @@ extern "C" int mvr_posegraph_optimize(const double* R_pair, const double* t_pair
   a.R = R; a.t = t; a.fs = f_sstride;
   a.member = member; a.cost = cost; a.iters = iters; a.status = status; a.trace = trace;
   a.ws = static_cast<double*>(workspace);
-  a.ws_stride = 43 * (int64_t)max_edges + (6 * (int64_t)max_frags + 1) * 6 * (int64_t)max_frags;
-  hipLaunchKernelGGL(mvr::posegraph_kernel, dim3(S), dim3(mvr::kPgThreads), 0, stream, a);
+  a.ws_stride = 43 * (int64_t)max_edges + (6 * (int64_t)max_frags + 1) * 6 * (int64_t)max_frags + extra;
+  *launch = true;
+  return MVR_OK;
+}
+
+extern "C" int mvr_posegraph_optimize(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w,
+                                      const double* info, int64_t e_sstride, const int32_t* n_edges,
+                                      const int32_t* n_frags, int S, int max_frags, int max_edges, int anchor,
+                                      const double* R0, const double* t0, int max_iters, double lambda0,
+                                      double tol_cost, double tol_step, double* R, double* t, int64_t f_sstride,
+                                      int32_t* member, double* cost, int32_t* iters, int32_t* status, double* trace,
+                                      void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  mvr::PgArgs a{};
+  bool launch;
+  const int rc = pg_arguments(R_pair, t_pair, ij, w, info, e_sstride, n_edges, n_frags, S, max_frags, max_edges, anchor,
+                              R0, t0, max_iters, lambda0, tol_cost, tol_step, R, t, f_sstride, member, cost, iters,
+                              status, trace, workspace, workspace_bytes,
+                              mvr_posegraph_workspace_bytes(S, max_frags, max_edges), 0, a, &launch);
+  if (rc != MVR_OK || !launch) return rc;
+  hipLaunchKernelGGL(mvr::posegraph_kernel<false>, dim3(S), dim3(mvr::kPgThreads), 0, stream, a);
+  MVR_CHECK_LAUNCH();
+  return MVR_OK;
+}
+
+extern "C" int mvr_posegraph_optimize_lp(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w,
+                                         const double* info, const int32_t* uncertain, int64_t e_sstride,
+                                         const int32_t* n_edges, const int32_t* n_frags, int S, int max_frags,
+                                         int max_edges, int anchor, const double* R0, const double* t0, int max_iters,
+                                         double lambda0, double tol_cost, double tol_step, double mu_scale, double* R,
+                                         double* t, int64_t f_sstride, int32_t* member, double* cost, int32_t* iters,
+                                         int32_t* status, double* trace, double* line, double* mu, void* workspace,
+                                         size_t workspace_bytes, hipStream_t stream) {
+  if (!(mu_scale > 0.0) || !isfinite(mu_scale)) return MVR_EINVAL;
+  mvr::PgLpArgs a{};
+  bool launch;
+  const int rc = pg_arguments(R_pair, t_pair, ij, w, info, e_sstride, n_edges, n_frags, S, max_frags, max_edges, anchor,
+                              R0, t0, max_iters, lambda0, tol_cost, tol_step, R, t, f_sstride, member, cost, iters,
+                              status, trace, workspace, workspace_bytes,
+                              mvr_posegraph_lp_workspace_bytes(S, max_frags, max_edges), 2 * (int64_t)max_edges, a,
+                              &launch);
+  if (rc != MVR_OK || !launch) return rc;
+  if (max_edges > 0 && !line) return MVR_EINVAL;  a.unc = uncertain; a.mu_scale = mu_scale; a.line = line; a.mu = mu;
+  hipLaunchKernelGGL(mvr::posegraph_kernel<true>, dim3(S), dim3(mvr::kPgThreads), 0, stream, a);
   MVR_CHECK_LAUNCH();
   return MVR_OK;
 }

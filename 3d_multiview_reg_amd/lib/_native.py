@@ -126,6 +126,11 @@ _SIGS = {
     "mvr_posegraph_optimize": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                        c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp,
                                        c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "mvr_posegraph_lp_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "mvr_posegraph_optimize_lp": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int,
+                                          c_int, c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_size, c_vp]),
     "mvr_fuse_scene_workspace_bytes": (c_size, [c_i64]),
     "mvr_fuse_scene": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, ctypes.c_double, c_vp, c_size, c_vp, c_vp,
                                c_vp, c_vp, c_vp, c_vp]),

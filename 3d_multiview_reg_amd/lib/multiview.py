@@ -117,14 +117,18 @@ def synchronize(R_pair, t_pair, pairs, n_frags, weights=None, anchor=0, irls_ite
 
 
 PG_STATUS_NOT_CONNECTED, PG_STATUS_ITERATION_CAP, PG_STATUS_EDGE_IGNORED, PG_STATUS_FACTORISATION = 1, 2, 4, 8
+PG_STATUS_LINE_PROCESS_OFF = 16
 
 
 def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=0, max_iters=20, lambda0=1e-6,
-                        tol_cost=1e-9, tol_step=1e-10, return_trace=False, n_frags=None, n_edges=None):
+                        tol_cost=1e-9, tol_step=1e-10, return_trace=False, n_frags=None, n_edges=None,
+                        line_process=False, uncertain=None, preference_loop_closure=1.0,
+                        max_correspondence_distance=None, edge_prune_threshold=0.25, prune_passes=2):
     """Refine poses jointly over SE(3) with per-edge information matrices (batched over scenes, one launch;
     csrc/posegraph.hip mvr_posegraph_optimize): Levenberg-Marquardt on sum_k w_k xi_k^T info_k xi_k,
     xi_k = (v, omega) of M_j^-1 M_i T_k^-1, from the poses `synchronize` returns, the anchor held.  The stage of
-    Open3D's global_optimization; Open3D parity is unpinned, there is no line process or robust kernel.
+    Open3D's global_optimization; Open3D parity is unpinned.  Without line_process there is no robust kernel: a
+    wrong edge is held back only by its weight.
 
     One scene: R [N,3,3], t [N,3] (the initial poses), R_pair [E,3,3], t_pair [E,3] (or [E,3,1]), pairs [E,2],
     info [E,6,6] (or [E,36]) in the (translation, rotation) order of lib.icp.information_matrix, weights [E] or None
@@ -137,9 +141,33 @@ def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=
     Returns a dict of fp64 R [N,3,3], t [N,3], int32 member [N], fp64 cost [2] (initial, final), int32 iters and
     status (PG_STATUS_* bits) and, with return_trace, fp64 trace [max_iters + 1]: the cost at the start and after
     every trial, -1 after the last; a batch adds a leading [S].  The outputs stay on the device when R was on the
-    device; otherwise they come back on the host (numpy for numpy inputs)."""
+    device; otherwise they come back on the host (numpy for numpy inputs).
+
+    line_process=True is Open3D's global_optimization with its line process and edge pruning (mvr_posegraph_optimize_lp,
+    DESIGN.md 4.22a; tests/posegraph_lp_oracle.py is the normative text): every uncertain edge (uncertain [E] /
+    [S,E] / per-scene list, non-zero = a loop closure; None: every edge) carries a weight l = (mu / (mu + r))^2,
+    r = w xi^T info xi, mu = preference_loop_closure * max_correspondence_distance^2 * the mean info[0, 0] of the
+    uncertain edges; max_correspondence_distance (the distance the information matrices were built with) is then
+    required.  prune_passes times: optimise, give the uncertain edges with l < edge_prune_threshold weight 0,
+    continue from the result (Open3D does this twice); prune_passes=0 is one optimisation without pruning.  The dict
+    is the last pass's (cost [2]: that pass's initial and final cost) and adds fp64 line [E] (the l of the last pass
+    in which the edge counted, 1 for a certain edge, 0 for one that never counted), bool kept [E] (False: pruned),
+    fp64 mu (the last pass's) and passes: a list of per-pass dicts of iters, status and cost.  Status bit
+    PG_STATUS_LINE_PROCESS_OFF: mu was not positive and finite, the pass ran with l = 1."""
     if int(max_iters) < 0:
         raise ValueError("optimize_pose_graph: max_iters must not be negative")
+    if line_process:
+        if max_correspondence_distance is None:
+            raise ValueError("optimize_pose_graph: line_process needs max_correspondence_distance, the distance the "
+                             "information matrices were built with")
+        mu_scale = float(preference_loop_closure) * float(max_correspondence_distance) ** 2
+        if not (mu_scale > 0.0 and mu_scale < float("inf")):
+            raise ValueError("optimize_pose_graph: preference_loop_closure and max_correspondence_distance must be "
+                             "finite and positive")
+        if not 0.0 <= float(edge_prune_threshold) <= 1.0:
+            raise ValueError("optimize_pose_graph: edge_prune_threshold must lie in [0, 1]")
+        if int(prune_passes) < 0:
+            raise ValueError("optimize_pose_graph: prune_passes must not be negative")
     if not (float(lambda0) >= 0.0 and float(lambda0) < float("inf")):
         raise ValueError("optimize_pose_graph: lambda0 must be finite and not negative")
     if not (tol_cost >= 0.0 and tol_step >= 0.0):
@@ -161,7 +189,8 @@ def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=
 
     if lists is not None:   # per-scene lists -> padded
         S = len(lists)
-        others = (t, R_pair, t_pair, pairs, info) + (() if weights is None else (weights,))
+        others = (t, R_pair, t_pair, pairs, info) + (() if weights is None else (weights,)) + \
+            (() if not line_process or uncertain is None else (uncertain,))
         if any(_as_list(x) is None or len(x) != S for x in others):
             raise ValueError("optimize_pose_graph: the per-scene lists must have one entry per scene")
         R0s = [f64(x, (3, 3)) for x in R]
@@ -175,6 +204,14 @@ def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=
         ij = torch.zeros(S, Emax, 2, dtype=torch.int32, device=dev)
         lam = torch.zeros(S, Emax, 36, dtype=torch.float64, device=dev)
         w = None if weights is None else torch.zeros(S, Emax, dtype=torch.float64, device=dev)
+        unc = None
+        if line_process and uncertain is not None:
+            unc = torch.zeros(S, Emax, dtype=torch.int32, device=dev)
+            for s in range(S):
+                us = torch.as_tensor(uncertain[s]).reshape(-1)
+                if us.shape[0] != ne[s]:
+                    raise ValueError("optimize_pose_graph: scene %d: one uncertain flag per edge" % s)
+                unc[s, :ne[s]] = (us != 0).to(dev, torch.int32)
         for s in range(S):
             ts, tps, ijs, ls = f64(t[s], (3,)), f64(t_pair[s], (3,)), torch.as_tensor(pairs[s]).reshape(-1, 2), \
                 f64(info[s], (36,))
@@ -211,9 +248,11 @@ def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=
             lam = torch.as_tensor(info).to(dev, torch.float64).reshape(S, Emax, 36).contiguous()
             w = None if weights is None else \
                 torch.as_tensor(weights).to(dev, torch.float64).reshape(S, Emax).contiguous()
+            unc = None if not line_process or uncertain is None else \
+                (torch.as_tensor(uncertain).to(dev) != 0).to(torch.int32).reshape(S, Emax).contiguous()
         except RuntimeError:
-            raise ValueError("optimize_pose_graph: t must hold one row per pose; t_pair, pairs, info and weights "
-                             "one per edge") from None
+            raise ValueError("optimize_pose_graph: t must hold one row per pose; t_pair, pairs, info, weights and "
+                             "uncertain one per edge") from None
         nf = [Fmax] * S if n_frags is None else [int(v) for v in torch.as_tensor(n_frags).reshape(-1).tolist()]
         ne = [Emax] * S if n_edges is None else [int(v) for v in torch.as_tensor(n_edges).reshape(-1).tolist()]
         if len(nf) != S or min(nf + [0]) < 0 or max(nf + [0]) > Fmax:
@@ -233,6 +272,50 @@ def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=
     cost = torch.zeros(S, 2, dtype=torch.float64, device=dev)
     iters, status = (torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2))
     trace = torch.full((S, rows), -1.0, dtype=torch.float64, device=dev) if return_trace else None
+    if line_process:
+        L = N.lib()
+        line = torch.zeros(S, Emax, dtype=torch.float64, device=dev)
+        kept = torch.ones(S, Emax, dtype=torch.bool, device=dev)
+        mu = torch.zeros(S, dtype=torch.float64, device=dev)
+        passes = []
+        w = torch.ones(S, Emax, dtype=torch.float64, device=dev) if w is None else w.clone()
+        flag = torch.ones(S, Emax, dtype=torch.bool, device=dev) if unc is None else unc != 0
+        live = torch.arange(Emax, device=dev)[None, :] < n_e[:, None].to(torch.int64)
+        for p in range(max(int(prune_passes), 1)):
+            if p:
+                R0, t0 = Ro.clone(), to.clone()
+            l_p = torch.zeros(S, Emax, dtype=torch.float64, device=dev)
+            if S and Fmax:
+                ws = N.workspace(L.mvr_posegraph_lp_workspace_bytes(S, Fmax, Emax), dev)
+                N.check(L.mvr_posegraph_optimize_lp(
+                    N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(lam), N.ptr(unc), Emax, N.ptr(n_e), N.ptr(n_f), S,
+                    Fmax, Emax, int(anchor), N.ptr(R0), N.ptr(t0), int(max_iters), float(lambda0), float(tol_cost),
+                    float(tol_step), mu_scale, N.ptr(Ro), N.ptr(to), Fmax, N.ptr(member), N.ptr(cost), N.ptr(iters),
+                    N.ptr(status), N.ptr(trace), N.ptr(l_p), N.ptr(mu), N.ptr(ws), ws.numel(), N.stream()),
+                    "mvr_posegraph_optimize_lp")
+            passes.append({"iters": iters.clone(), "status": status.clone(), "cost": cost.clone()})
+            counted = (l_p > 0.0) & live             # a counted edge's l is positive (1 for a certain one)
+            line = torch.where(counted, l_p, line)
+            if int(prune_passes) > 0:
+                drop = counted & flag & (l_p < float(edge_prune_threshold))
+                w = torch.where(drop, torch.zeros_like(w), w)
+                kept &= ~drop
+        out = {"R": Ro, "t": to, "member": member, "cost": cost, "iters": iters, "status": status}
+        if return_trace:
+            out["trace"] = trace
+        out.update(line=line, kept=kept, mu=mu)
+
+        def shape(d):
+            if not batched:
+                d = {k: v[0] for k, v in d.items()}
+            if not on_dev:
+                d = {k: v.cpu() for k, v in d.items()}
+                if was_numpy:
+                    d = {k: v.numpy() for k, v in d.items()}
+            return d
+        out = shape(out)
+        out["passes"] = [shape(d) for d in passes]
+        return out
     if S and Fmax:
         L = N.lib()
         ws = N.workspace(L.mvr_posegraph_workspace_bytes(S, Fmax, Emax), dev)
@@ -391,7 +474,8 @@ def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
 def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=None, viewpoints=None, downsample=True,
                    dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
-                   min_frags=1, min_points=1, ransac_checkers=False):
+                   min_frags=1, min_points=1, ransac_checkers=False, line_process=False,
+                   preference_loop_closure=1.0):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
@@ -405,12 +489,14 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
          (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
       6. lib.icp.icp_refine (method 'point_to_point' / 'point_to_plane') or gicp_refine ('generalized') on the kept
          pairs;  7. lib.icp.information_matrix;  8. synchronize(irls_iters=5);  9. optimize_pose_graph with the
-         IRLS weights;  10. fuse_scene(voxel fuse_voxel, None: voxel_size) over the fragments connected to `anchor`.
+         IRLS weights (line_process: with Open3D's line process and edge pruning, every kept pair an uncertain edge,
+         preference_loop_closure, and the distance the information matrices used: icp_max_dist, None: the index's
+         cell);  10. fuse_scene(voxel fuse_voxel, None: voxel_size) over the fragments connected to `anchor`.
     Returns a dict of R [n,3,3], t [n,3] and poses [n,4,4] (numpy fp64, fragment -> the anchor's frame), member [n],
     pairs: a dict of numpy arrays over the pairs i < j (pairs [P,2], T_coarse [P,4,4], overlap [P], kept bool [P],
     T [P,4,4] the refined estimate (the coarse one where the pair was not kept), fitness and rmse [P] of the
-    refinement, 0 where not kept), sync and refined (the dicts of synchronize and optimize_pose_graph), fo, and
-    scene (the dict of fuse_scene)."""
+    refinement, 0 where not kept; with line_process also pruned bool [P]: the pose graph dropped the pair), sync and
+    refined (the dicts of synchronize and optimize_pose_graph), fo, and scene (the dict of fuse_scene)."""
     from lib.fpfh import register_fpfh
     from lib.icp import gicp_refine, icp_refine, information_matrix
     from lib.overlap import FragmentOverlap
@@ -440,7 +526,11 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     sync = synchronize(Tk[:, :3, :3], Tk[:, :3, 3], kp, n, anchor=anchor, irls_iters=5)
     refined = optimize_pose_graph(np.asarray(sync["R"]), np.asarray(sync["t"]), Tk[:, :3, :3], Tk[:, :3, 3], kp,
                                   np.asarray(info["info"]), np.asarray(sync["weights"]), anchor=anchor,
-                                  max_iters=refine_iters)
+                                  max_iters=refine_iters,
+                                  **({} if not line_process else dict(
+                                      line_process=True, preference_loop_closure=preference_loop_closure,
+                                      max_correspondence_distance=float(fo.r if icp_max_dist is None
+                                                                        else icp_max_dist))))
     R, t = np.asarray(refined["R"], dtype=np.float64), np.asarray(refined["t"], dtype=np.float64)
     member = np.asarray(refined["member"])
     scene = fuse_scene(fo, R, t, voxel_size if fuse_voxel is None else fuse_voxel, member=member,
@@ -452,5 +542,9 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     T[kept], fitness[kept], rmse[kept] = Tk, np.asarray(ref["fitness"]), np.asarray(ref["rmse"])
     records = {"pairs": pairs, "T_coarse": T_coarse, "overlap": overlap, "kept": kept, "T": T, "fitness": fitness,
                "rmse": rmse}
+    if line_process:
+        pruned = np.zeros(P, dtype=bool)
+        pruned[kept] = ~np.asarray(refined["kept"], dtype=bool)
+        records["pruned"] = pruned
     return {"R": R, "t": t, "poses": poses, "member": member, "pairs": records, "sync": sync, "refined": refined,
             "fo": fo, "scene": scene}

@@ -8,10 +8,12 @@ refinement and the fused cloud, all on the GPU.  Writes into --out
               3DMatch log convention of the pairwise benchmark's traj.txt, readable by scripts/multiview_sync.py),
   scene.ply   the fused cloud with normals (scripts/fuse_scene.py fuses again at another voxel size from poses.txt).
 --init traj.txt: a trajectory in that convention holding every pair i < j replaces the FPFH stage.
+--line_process: the pose-graph refinement runs with Open3D's line process and edge pruning (every pair that passed the
+gate is an uncertain edge); the pairs it pruned are counted in the printed line.
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
            [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
-           [--checkers]
+           [--checkers] [--line_process [--preference_loop_closure 1.0]]
 """
 import argparse
 import os
@@ -57,6 +59,9 @@ def parser():
     ap.add_argument("--seed", type=int, default=0, help="RANSAC draw stream seed")
     ap.add_argument("--checkers", action="store_true",
                     help="RANSAC with the edge-length and distance checkers: 3-point samples, 100000 draws")
+    ap.add_argument("--line_process", action="store_true",
+                    help="pose-graph refinement with the line process and edge pruning of Open3D's global_optimization")
+    ap.add_argument("--preference_loop_closure", type=float, default=1.0, help="--line_process: Open3D's option")
     return ap
 
 
@@ -69,6 +74,8 @@ def check_args(ap, a):
         ap.error("--min_frags must be at least 1")
     if not 0 <= a.anchor < len(a.fragments):
         ap.error("--anchor outside the fragments")
+    if not a.preference_loop_closure > 0.0:
+        ap.error("--preference_loop_closure must be positive")
     return a
 
 
@@ -79,7 +86,9 @@ def main(argv=None):
     frags = [read_ply_xyz(f) for f in a.fragments]
     init = None if a.init is None else read_init(a.init, len(frags))
     res = register_scene(frags, a.voxel_size, method=a.icp_method, init=init, dataset=a.dataset, seed=a.seed,
-                         anchor=a.anchor, min_frags=a.min_frags, ransac_checkers=a.checkers)
+                         anchor=a.anchor, min_frags=a.min_frags, ransac_checkers=a.checkers,
+                         **({} if not a.line_process else dict(line_process=True,
+                                                               preference_loop_closure=a.preference_loop_closure)))
     ensure_dir(a.out)
     write_poses(res["poses"], os.path.join(a.out, "poses.txt"))
     rec = res["pairs"]
@@ -93,6 +102,8 @@ def main(argv=None):
           % (len(frags), int(rec["kept"].sum()), len(meta), int(np.asarray(res["member"]).sum()), a.anchor,
              float(res["refined"]["cost"][0]), float(res["refined"]["cost"][1]), len(scene["xyz"]), a.voxel_size,
              a.out))
+    if a.line_process:
+        print("line process: %d of the %d gated pairs pruned" % (int(rec["pruned"].sum()), int(rec["kept"].sum())))
     return res
 
 

@@ -555,7 +555,8 @@ int mvr_feat_match(const float* F, int C, const int64_t* off, int B, int64_t M, 
 /* ------------------------------------------------------------------------
  * Pose-graph refinement over SE(3), batched over scenes (csrc/posegraph.hip): the Levenberg-
  * Marquardt stage of Open3D's global_optimization / Choi et al. 2015, restated from the maths (Open3D parity is
- * unpinned; no line process or robust kernel).  tests/posegraph_oracle.py is the normative text.
+ * unpinned; this entry has no line process or robust kernel, mvr_posegraph_optimize_lp below has the line process).
+ * tests/posegraph_oracle.py is the normative text.
  *   Scenes, edges, fragments, strides and conventions are mvr_sync_poses': edge e = (i, j) with x_j ~ T_e x_i,
  *   T_e = (R_pair, t_pair); pose M_f: X = R_f x_f + t_f.  info [., 36]: the edge's 6 x 6 matrix in (v, omega) order
  *   (mvr_pair_information's), rows as R_pair; (info + info^T) / 2 is what is used.  R0 [., 9], t0 [., 3]: the initial
@@ -599,6 +600,47 @@ int mvr_posegraph_optimize(const double* R_pair, const double* t_pair, const int
                            int max_iters, double lambda0, double tol_cost, double tol_step, double* R, double* t,
                            int64_t f_sstride, int32_t* member, double* cost, int32_t* iters, int32_t* status,
                            double* trace, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Pose-graph refinement with a line process on the uncertain edges (csrc/posegraph.hip): the robust
+ * stage of Open3D's global_optimization / Choi et al. 2015, restated from the maths (Open3D parity is unpinned).
+ * tests/posegraph_lp_oracle.py is the normative text.  Everything not said here (conventions, residual xi_e,
+ * (info + info^T) / 2, members, ignored edges, the update, the Levenberg-Marquardt trial, stopping rules, status bits
+ * 1 / 2 / 4 / 8, the trace, determinism, the NULL and stride rules) is mvr_posegraph_optimize's.
+ *   uncertain [., 1] int32 (rows as R_pair; may be NULL: every edge is uncertain): non-zero marks a loop-closure
+ *   edge.  An edge "counts" when its weight is positive after the validity and membership rules.
+ *   r_e = w_e xi_e^T info_e xi_e.  mu = mu_scale * mean of info_e[0] over the counted uncertain edges (info[0] is the
+ *   correspondence count in the (v, omega) order; Open3D's info(3, 3) in its (omega, v) order).  mu_scale =
+ *   preference_loop_closure * max_correspondence_distance^2 in Open3D's terms; the caller forms the product.
+ *   l_e = s_e^2, s_e = mu / (mu + r_e), for a counted uncertain edge; 1 for a counted certain edge.
+ *   Cost c = (sum_certain r_e + sum_uncertain l_e r_e) + mu sum_uncertain (s_e - 1)^2, each sum in the fixed order;
+ *   at the closed-form l this is the Geman-McClure cost sum_certain r_e + sum_uncertain mu r_e / (mu + r_e).
+ *   Start: l in closed form at the initial poses, c from it.  A trial builds H and g with the weights w_e l_e, l held,
+ *   and evaluates the candidate's cost c' with the same held l (and the held third sum); c' < c accepts.  After an
+ *   accepted trial l is recomputed in closed form at the new poses (from the r_e the candidate's cost pass formed),
+ *   which gives c'' <= c'; the held cost becomes c'', lambda /= 10, and the tol_cost test is c - c'' <= tol_cost c.
+ *   After a rejected trial lambda *= 10 and l stays.  Every cost in the trace is thus a Geman-McClure cost, and the
+ *   trace does not rise.
+ *   Status bit 16: a counted uncertain edge exists but mu is not positive and finite (e.g. all-zero information on
+ *   the uncertain edges); the scene then runs with every edge certain, l = 1.
+ *   Without a counted uncertain edge (uncertain all zero) R, t, member, cost, iters, status and trace equal
+ *   mvr_posegraph_optimize's byte for byte: the second and third sums are 0.0 and every weight is w_e * 1.0.
+ *   Outputs beyond mvr_posegraph_optimize's: line [., 1] fp64 (rows as R_pair): the final l_e, 1 for a counted
+ *   certain edge, 0 for an edge that does not count and for every edge of an invalid scene; mu [S] (may be NULL): mu
+ *   as computed, 0 when no uncertain edge counts.
+ *   workspace (8-byte aligned) >= mvr_posegraph_lp_workspace_bytes(S, max_frags, max_edges): mvr_posegraph_optimize's
+ *   plus l and r, two doubles per edge.
+ *   MVR_EINVAL: as mvr_posegraph_optimize; a mu_scale that is not finite and positive (checked first); a NULL line
+ *   with max_edges > 0 (where mvr_posegraph_optimize's pointers are required).
+ * ---------------------------------------------------------------------- */
+size_t mvr_posegraph_lp_workspace_bytes(int S, int max_frags, int max_edges);
+int mvr_posegraph_optimize_lp(const double* R_pair, const double* t_pair, const int32_t* ij, const double* w,
+                              const double* info, const int32_t* uncertain, int64_t e_sstride, const int32_t* n_edges,
+                              const int32_t* n_frags, int S, int max_frags, int max_edges, int anchor, const double* R0,
+                              const double* t0, int max_iters, double lambda0, double tol_cost, double tol_step,
+                              double mu_scale, double* R, double* t, int64_t f_sstride, int32_t* member, double* cost,
+                              int32_t* iters, int32_t* status, double* trace, double* line, double* mu,
+                              void* workspace, size_t workspace_bytes, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Scene fusion (csrc/fuse.hip): the registered fragments mapped by their poses into one frame and

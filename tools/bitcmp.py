@@ -3,7 +3,10 @@
                                              logits, scores, R, t), one scene step of the bench workload (records
                                              of all 435 pairs) and the radius-index refinements (the three ICP
                                              methods and mvr_pair_information on the tests' scene and small shapes:
-                                             every output), save them
+                                             every output) and the pose-graph refinement (mvr_posegraph_optimize
+                                             on seeded scenes of tests/posegraph_oracle.py: every output), save
+                                             them; `dump <out.npz> posegraph` (or oanet, scene, refinements): only
+                                             those sections
   python tools/bitcmp.py cmp <a.npz> <b.npz> count the elements that differ bit for bit (exit 1 if any)"""
 import os
 import sys
@@ -47,7 +50,44 @@ def refinements():
     return res
 
 
-def dump(path):
+def posegraph():
+    """every output of optimize_pose_graph (the plain entry, mvr_posegraph_optimize) on seeded scenes of
+    tests/posegraph_oracle.py, alone and as one ragged batch"""
+    import posegraph_oracle as PO
+    from lib.multiview import optimize_pose_graph
+    keys = ("R0", "t0", "R_pair", "t_pair", "ij", "info", "w")
+    C = PO.cases()
+    res = {}
+    runs = [("n30_noisy", dict(max_iters=6, tol_cost=0.0, tol_step=0.0)), ("n30_noisy", {})]
+    runs += [(n, C[n][1]) for n in ("n30_noisy_tol", "n64_noisy", "reject", "bad_edges", "edges_257", "n30_exact")]
+    for name, kw in runs:
+        tag = "pg_%s%s" % (name, "" if kw else "_default")
+        for k, v in optimize_pose_graph(*(C[name][0][k] for k in keys), return_trace=True, **kw).items():
+            res["%s_%s" % (tag, k)] = np.asarray(v)
+    scs = [C[n][0] for n in ("n3_noisy", "n30_noisy", "bad_edges", "disconnected")]
+    out = optimize_pose_graph(*([s[k] for s in scs] for k in keys), return_trace=True, max_iters=3, tol_cost=0.0,
+                              tol_step=0.0)
+    for k, v in out.items():
+        res["pg_batch_%s" % k] = np.asarray(v)
+    return res
+
+
+SECTIONS = ("oanet", "scene", "refinements", "posegraph")
+
+
+def dump(path, sections=SECTIONS):
+    res = {}
+    if "posegraph" in sections:
+        res.update(posegraph())
+    if "refinements" in sections:
+        res.update(refinements())
+    if "oanet" in sections or "scene" in sections:
+        res.update(network(sections))
+    np.savez(path, **res)
+    print("dumped", path, {k: v.shape for k, v in res.items()})
+
+
+def network(sections):
     import json
     import torch
     import bench
@@ -58,15 +98,15 @@ def dump(path):
     xs, _, _ = synth_correspondences(32, 5000, seed=p["xs_seed"], inlier_lo=p["inlier_lo"], inlier_hi=p["inlier_hi"])
     out, _ = bench._oanet_golden(dev, "oanet_full_train_strict.npz", p["weights_seed"], xs)
     res = {}
-    for i in range(2):
-        for k in ("logits", "scores", "rot_est", "trans_est"):
-            res["%s%d" % (k, i)] = out[k][i].detach().cpu().numpy()
-    wl = bench.SceneWorkload(dev, 0)
-    with torch.no_grad():
-        res["scene_records"] = wl.step().cpu().numpy()
-    res.update(refinements())
-    np.savez(path, **res)
-    print("dumped", path, {k: v.shape for k, v in res.items()})
+    if "oanet" in sections:
+        for i in range(2):
+            for k in ("logits", "scores", "rot_est", "trans_est"):
+                res["%s%d" % (k, i)] = out[k][i].detach().cpu().numpy()
+    if "scene" in sections:
+        wl = bench.SceneWorkload(dev, 0)
+        with torch.no_grad():
+            res["scene_records"] = wl.step().cpu().numpy()
+    return res
 
 
 def cmp(a, b):
@@ -83,6 +123,6 @@ def cmp(a, b):
 
 if __name__ == "__main__":
     if sys.argv[1] == "dump":
-        dump(sys.argv[2])
+        dump(sys.argv[2], tuple(sys.argv[3:]) or SECTIONS)
     else:
         sys.exit(1 if cmp(sys.argv[2], sys.argv[3]) else 0)

@@ -11,7 +11,10 @@
                 tolerances 0) and a run at the default tolerances; beside them mvr_sync_poses (one pass) on the same
                 edges, the numpy oracle's whole loop, and LAPACK alone on the oracle's system (numpy cholesky + two
                 triangular solves of 6N unknowns, one trial's solve)
-usage: python tools/posegraph_micro.py [--reps 15] [--skip_info] [--skip_graph]"""
+  line process  --line_process: mvr_posegraph_optimize_lp (every edge uncertain, mu_scale 0.0025) beside
+                mvr_posegraph_optimize on the same scenes, the two alternating call by call, at 2 and at 6 trials:
+                the time per trial of each and their ratio
+usage: python tools/posegraph_micro.py [--reps 15] [--skip_info] [--skip_graph] [--line_process]"""
 import argparse
 import os
 import sys
@@ -93,7 +96,7 @@ def information(reps):
           % (stats(b) + (reps, int(nc2.min()), int(nc2.max()))), flush=True)
 
 
-def graph(n, reps):
+def graph(n, reps, line_process=False):
     import posegraph_oracle as PO
     d = torch.device("cuda")
     L = N.lib()
@@ -122,6 +125,50 @@ def graph(n, reps):
                                             N.ptr(status), None, N.ptr(ws), ws.numel(), N.stream()) == 0
         ms = timed(run, reps)
         return stats(ms), its.tolist(), sorted(set(status.tolist())), cost[0].tolist()
+
+    def pair(S, iters):
+        """(plain, line process) timings of `iters` trials, alternating call by call"""
+        n_e = torch.full((S,), E, dtype=torch.int32, device=d)
+        n_f = torch.full((S,), n, dtype=torch.int32, device=d)
+        R = torch.empty(S, n, 9, dtype=torch.float64, device=d)
+        t = torch.empty(S, n, 3, dtype=torch.float64, device=d)
+        cost = torch.empty(S, 2, dtype=torch.float64, device=d)
+        line = torch.empty(S, E, dtype=torch.float64, device=d)
+        its, status = (torch.empty(S, dtype=torch.int32, device=d) for _ in range(2))
+        ws = torch.empty(L.mvr_posegraph_lp_workspace_bytes(S, n, E), dtype=torch.uint8, device=d)
+
+        def plain():
+            assert L.mvr_posegraph_optimize(N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(info), E, N.ptr(n_e),
+                                            N.ptr(n_f), S, n, E, 0, N.ptr(R0), N.ptr(t0), iters, 1e-6, 0.0, 0.0,
+                                            N.ptr(R), N.ptr(t), n, None, N.ptr(cost), N.ptr(its), N.ptr(status), None,
+                                            N.ptr(ws), ws.numel(), N.stream()) == 0
+
+        def lp():
+            assert L.mvr_posegraph_optimize_lp(N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(info), None, E,
+                                               N.ptr(n_e), N.ptr(n_f), S, n, E, 0, N.ptr(R0), N.ptr(t0), iters, 1e-6,
+                                               0.0, 0.0, 0.0025, N.ptr(R), N.ptr(t), n, None, N.ptr(cost), N.ptr(its),
+                                               N.ptr(status), None, N.ptr(line), None, N.ptr(ws), ws.numel(),
+                                               N.stream()) == 0
+        for _ in range(3):
+            plain()
+            lp()
+        torch.cuda.synchronize()
+        a, b = [], []
+        for _ in range(reps):
+            a += timed(plain, 1, warm=0)
+            b += timed(lp, 1, warm=0)
+        assert its.tolist() == [iters] * S
+        return stats(a), stats(b)
+
+    if line_process:
+        for S in (1, 8):
+            (p2, l2), (p6, l6) = pair(S, 2), pair(S, 6)
+            tp_, tl_ = (p6[0] - p2[0]) / 4.0, (l6[0] - l2[0]) / 4.0
+            print("line process %d scene%s x %d fragments x %d edges: plain 2 trials %.3f ms (min %.3f, max %.3f), 6 "
+                  "trials %.3f ms (min %.3f, max %.3f) -> %.4f ms per trial; line process 2 trials %.3f ms (min %.3f, "
+                  "max %.3f), 6 trials %.3f ms (min %.3f, max %.3f) -> %.4f ms per trial; ratio %.4f"
+                  % ((S, "s" if S > 1 else "", n, E) + p2 + p6 + (tp_,) + l2 + l6 + (tl_, tl_ / tp_)), flush=True)
+        return
 
     for S in (1, 8):
         (m2, lo2, hi2), _, _, _ = bench(S, 2, 0.0, 0.0)
@@ -171,12 +218,14 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--skip_info", action="store_true")
     ap.add_argument("--skip_graph", action="store_true")
+    ap.add_argument("--line_process", action="store_true",
+                    help="pose graph: only mvr_posegraph_optimize_lp beside mvr_posegraph_optimize, alternating")
     a = ap.parse_args()
     if not a.skip_info:
         information(a.reps)
     if not a.skip_graph:
         for n in (30, 60):
-            graph(n, a.reps)
+            graph(n, a.reps, a.line_process)
 
 
 if __name__ == "__main__":
