@@ -10,6 +10,20 @@
 // one lane solves the 3x3 SVD by one-sided Jacobi in fp64, and a second pass
 // (L2-resident re-read) writes the fp32 residuals.
 //
+// Origin of the moments.  The centred covariance comes out of raw moments, so for a cloud of spread 1 at
+// distance c from the origin every term is ~c^2 while the result is ~1: fp64 moments about the origin lose
+// 2 log10(c) digits (measured on an MI355X, fp64, 257 points, worst |R - R_oracle| of four pairs: 1.0e-12 at
+// c = 1e2, 3.1e-11 at 1e3, 4.7e-9 at 1e4), and a covariance that is itself tiny against the moments — one point,
+// where H = W (eps / (W + eps))^2 x1 x2^T — comes out as rounding noise in either precision (tr(R H) short of the
+// optimum by 1.7e-5 s0 in fp64, 9.4e-5 s0 in fp32).  Both instantiations therefore accumulate about the pair's first point,
+// o1 = x1[0], o2 = x2[0] (one address for the whole workgroup), as icp.hip does.  With x' = x - o, sums S' over
+// the shifted points and the reference's means mu = S / (W + eps) (utils.py:203-204 — NOT S / W):
+//   a = mu1 - o1 = (S1' + W o1) / (W + eps) - o1 = (S1' - eps o1) / (W + eps),   b = mu2 - o2 likewise,
+//   H = sum w (x1 - mu1)(x2 - mu2)^T = sum w (x1' - a)(x2' - b)^T = S12' - a S2'^T - S1' b^T + W a b^T,
+//   t = mu2 - R mu1 = (b + o2) - R (a + o1).
+// Every term is now of the size of the cloud's extent about its first point (the same fp64 clouds: 3.3e-15,
+// 8.9e-16, 6.1e-16).  The first point counts as origin whatever its weight: it has to lie with the cloud.
+//
 // HBM bytes per pair (algorithmic): N*(24 read xyz pairs + 4 read w + 4 write res)
 // (+4+4 when the guard rewrites w and its copy).
 #include "common.hpp"
@@ -59,7 +73,14 @@ __global__ __launch_bounds__(256) void procrustes_kernel(ProcrustesArgs<T> a) {
   const bool guard = sflag != 0;
   const T addw = (T)1 / (T)a.N;
 
-  // ---- moments: W, S1[3], S2[3], S12[3][3]
+  // ---- origin of the moments (header comment): the pair's first point
+  double o1[3] = {0.0, 0.0, 0.0}, o2[3] = {0.0, 0.0, 0.0};
+  if (a.N > 0) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { o1[i] = x1[i]; o2[i] = x2[i]; }
+  }
+
+  // ---- moments of the shifted points: W, S1[3], S2[3], S12[3][3]
   double m[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) m[i] = 0.0;
@@ -73,8 +94,8 @@ __global__ __launch_bounds__(256) void procrustes_kernel(ProcrustesArgs<T> a) {
     const T* p1 = x1 + (int64_t)n * a.x_ns;
     const T* p2 = x2 + (int64_t)n * a.x_ns;
     const double wd = wi;
-    const double u0 = p1[0], u1 = p1[1], u2 = p1[2];
-    const double v0 = p2[0], v1 = p2[1], v2 = p2[2];
+    const double u0 = p1[0] - o1[0], u1 = p1[1] - o1[1], u2 = p1[2] - o1[2];
+    const double v0 = p2[0] - o2[0], v1 = p2[1] - o2[1], v2 = p2[2] - o2[2];
     m[0] += wd;
     m[1] += wd * u0; m[2] += wd * u1; m[3] += wd * u2;
     m[4] += wd * v0; m[5] += wd * v1; m[6] += wd * v2;
@@ -90,16 +111,16 @@ __global__ __launch_bounds__(256) void procrustes_kernel(ProcrustesArgs<T> a) {
     if (a.normalize) scale = 1.0 / ((double)((T)m[0] + a.eps));
     const double W = m[0] * scale;
     const double den = W + (double)a.eps;  // utils.py:203-204
-    double mu1[3], mu2[3], S1[3], S2[3];
+    double mu1[3], mu2[3], S1[3], S2[3];   // mu: the means relative to the origin (a, b of the header comment)
     for (int i = 0; i < 3; ++i) {
       S1[i] = m[1 + i] * scale; S2[i] = m[4 + i] * scale;
-      mu1[i] = S1[i] / den; mu2[i] = S2[i] / den;
+      mu1[i] = (S1[i] - (double)a.eps * o1[i]) / den; mu2[i] = (S2[i] - (double)a.eps * o2[i]) / den;
     }
     double H[3][3];
     bool finite = true;
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) {
-        // sum w (x1-mu1)(x2-mu2)^T = S12 - mu1 S2^T - S1 mu2^T + W mu1 mu2^T
+        // sum w (x1'-mu1)(x2'-mu2)^T = S12 - mu1 S2^T - S1 mu2^T + W mu1 mu2^T
         H[i][j] = m[7 + 3 * i + j] * scale - mu1[i] * S2[j] - S1[i] * mu2[j] + W * mu1[i] * mu2[j];
         finite = finite && isfinite(H[i][j]);
       }
@@ -117,6 +138,7 @@ __global__ __launch_bounds__(256) void procrustes_kernel(ProcrustesArgs<T> a) {
       const double d = det3(VUt) < 0 ? -1.0 : 1.0;  // utils.py:225-227
       for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) R[i][j] = V[i][0] * U[j][0] + V[i][1] * U[j][1] + d * V[i][2] * U[j][2];
+      for (int i = 0; i < 3; ++i) { mu1[i] += o1[i]; mu2[i] += o2[i]; }
       for (int i = 0; i < 3; ++i) t[i] = mu2[i] - (R[i][0] * mu1[0] + R[i][1] * mu1[1] + R[i][2] * mu1[2]);
     }
     for (int i = 0; i < 3; ++i) {

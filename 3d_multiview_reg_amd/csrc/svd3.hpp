@@ -1,5 +1,14 @@
 // 3 x 3 SVD by one-sided Jacobi in fp64 and the 3 x 3 determinant, shared by the Procrustes / RANSAC kernels
-// (procrustes.hip) and the pose synchronisation (sync.hip).
+// (procrustes.hip, ransac_checked.hip), the ICP solve (icp.hip) and the pose synchronisation (sync.hip).
+//
+// H = U diag(S) V^T, S descending, V orthogonal; U's columns of singular values <= 1e-13 S[0] are completed (rank
+// 1: a unit vector orthogonal to u0; rank <= 2: u2 = u0 x u1), so U is orthogonal to rounding at every rank; the
+// zero matrix gives U = V = I.  Every threshold is relative to the matrix (|ga| <= 1e-15 sqrt(al be), tiny =
+// 1e-13 S[0]): scaling H by a power of two scales S and leaves U, V bit for bit — as long as al * be, a product of
+// two squared column norms, neither overflows nor underflows: entries within about 2^-250 .. 2^250.  Beyond that
+// the result is out of contract.  A column that an exactly rank-deficient matrix drives to zero keeps being rotated
+// (it shrinks by ~1e-16 per sweep, never orthogonal RELATIVE to its own norm) until it underflows or the 30 sweeps
+// are over; the result is the same (tests/test_gpu_procrustes.py, the zero-row matrices).
 #pragma once
 #include "common.hpp"
 #include <math.h>

@@ -57,7 +57,14 @@ int mvr_procrustes(const float* x1, const float* x2, int64_t x_pstride, int64_t 
                    int64_t w_pstride, const int32_t* guard_pos, float* w_copy, int64_t wc_pstride, int P, int N,
                    int normalize, float eps, float* R, float* t, float* res, int64_t res_pstride, float* res_copy,
                    int64_t rc_pstride, int32_t* status, int guard_group, mvr_stream_t stream);
-/* fp64 variant (fp64 inputs compute in fp64 in the reference, utils.py:164). */
+/* fp64 variant (fp64 inputs compute in fp64 in the reference, utils.py:164).  In both variants the covariance is
+ * accumulated in fp64 about the pair's first point (x1[p,0], x2[p,0]), not about the origin, so clouds far from
+ * the origin keep their digits: for 257 points of spread 1 at distance 1e4, R of mvr_procrustes_f64 was measured
+ * within 6.1e-16 of a two-pass long-double Kabsch on an MI355X (4.7e-9 with the moments about the origin); t
+ * follows R as mu2 - R mu1.  mvr_procrustes: R within 3e-8 of the same reference on the fp32-rounded inputs at
+ * distance 1e3, the rounding of R itself.  The first point serves as origin whatever its weight, so it must be
+ * representative of the cloud: a zero-weight first point far from the others (padding, an outlier at 1e6) costs
+ * the digits that its distance from the cloud has. */
 int mvr_procrustes_f64(const double* x1, const double* x2, int64_t x_pstride, int64_t x_nstride, double* w,
                        int64_t w_pstride, const int32_t* guard_pos, double* w_copy, int64_t wc_pstride, int P, int N,
                        int normalize, double eps, double* R, double* t, double* res, int64_t res_pstride,

@@ -1,6 +1,7 @@
 """Batched GPU RANSAC (csrc/procrustes.hip mvr_ransac, lib/utils.py run_ransac[_batch]) against the
 restatement of lib/utils.py:671-709 / Open3D 0.9 in oracle/ransac.py (Open3D itself: parity unpinned):
-  * every hypothesis (same counter-stream draws, Umeyama fit) within 1e-9 of the oracle's numpy-SVD fit;
+  * every hypothesis (same counter-stream draws, Umeyama fit) within 1e-9 of the oracle's numpy-SVD fit, and every
+    one, the rank-deficient draws left out of that comparison included, a finite proper rotation to 1e-12;
   * inlier counts / error sums of the GPU's own hypotheses, re-evaluated by the oracle in the kernel's fp64
     operation order: the selected iteration, fitness and rmse identical (bit for bit);
   * ragged per-pair counts (n < ransac_n -> identity, fitness 0), batch == per-pair calls;
@@ -59,6 +60,12 @@ def test_ransac_matches_oracle(gpu, n, iters):
         ok = [it for it in range(iters) if len(set(O.draws(11, p, it, 4, m))) >= 3]
         assert len(ok) > 0.9 * iters
         np.testing.assert_allclose(hyp[p][ok], own[ok], atol=1e-9)
+        # every hypothesis, the skipped draws included (their covariance has rank 1 or 0: the completion branches
+        # of jacobi_svd3), is a finite proper rotation
+        Rh = hyp[p][:, :9].reshape(iters, 3, 3)
+        assert np.all(np.isfinite(hyp[p]))
+        np.testing.assert_allclose(np.swapaxes(Rh, 1, 2) @ Rh, np.broadcast_to(np.eye(3), Rh.shape), rtol=0, atol=1e-12)
+        np.testing.assert_allclose(np.linalg.det(Rh), 1.0, rtol=0, atol=1e-12)
         # the selection over the GPU's hypotheses, re-evaluated on the host: identical
         assert best[p] == bo, (p, best[p], bo)
         assert fit[p] == fo and rmse[p] == ro, (p, fit[p], fo, rmse[p], ro)
@@ -69,10 +76,18 @@ def test_ragged_and_degenerate(gpu):
     x1, x2, _, _ = _corr(64, 0.5, seed=3)
     x1 = np.stack([x1] * 4)
     x2 = np.stack([x2] * 4)
-    T, fit, rmse, best, _ = _gpu(x1, x2, [0, 3, 4, 64], 5, 64, gpu)
+    T, fit, rmse, best, hyp = _gpu(x1, x2, [0, 3, 4, 64], 5, 64, gpu)
     for p in (0, 1):   # fewer correspondences than ransac_n: Open3D returns RegistrationResult()
         assert best[p] == -1 and fit[p] == 0.0 and rmse[p] == 0.0 and np.array_equal(T[p], np.eye(4))
     assert best[2] >= 0 and fit[2] > 0 and best[3] >= 0
+    # four draws out of four correspondences: most covariances have rank 2, 1 or 0; still proper rotations
+    distinct = [len(set(O.draws(5, 2, it, 4, 4))) for it in range(64)]
+    assert min(distinct) <= 2 and distinct.count(3) > 0
+    for p in (2, 3):
+        Rh = hyp[p][:, :9].reshape(64, 3, 3)
+        assert np.all(np.isfinite(hyp[p]))
+        np.testing.assert_allclose(np.swapaxes(Rh, 1, 2) @ Rh, np.broadcast_to(np.eye(3), Rh.shape), rtol=0, atol=1e-12)
+        np.testing.assert_allclose(np.linalg.det(Rh), 1.0, rtol=0, atol=1e-12)
 
 
 def test_batch_equals_single_calls(gpu):
