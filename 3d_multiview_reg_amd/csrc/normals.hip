@@ -70,35 +70,14 @@ __global__ __launch_bounds__(kNormalsThreads) void normals_kernel(RIndex ix, con
   const int64_t i = ix.sidx[s];
   const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
   const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  const double slack = 1e-9 * r, rad2 = radius * radius * (1.0 + 1e-9);
-  int64_t c[3];
-  double lo[3];   // distance to the lower neighbour cell along each axis; r - lo to the upper one
-  for (int e = 0; e < 3; ++e) {
-    const double cf = floor(p[e] / r);
-    c[e] = (int64_t)cf + OV_BIAS;
-    lo[e] = p[e] - cf * r;
-  }
   int n = 0;
   double m[3] = {0.0, 0.0, 0.0}, S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // sum e; sum e e^T: xx xy xz yy yz zz
-  for (int cell = 0; cell < 27; ++cell) {
-    const int dx = cell % 3 - 1, dy = (cell / 3) % 3 - 1, dz = cell / 9 - 1;
-    // a lower bound of the distance to that cell's box, shrunk by a slack far above the rounding of p / r
-    const double gx = dx == 0 ? 0.0 : fmax((dx < 0 ? lo[0] : r - lo[0]) - slack, 0.0);
-    const double gy = dy == 0 ? 0.0 : fmax((dy < 0 ? lo[1] : r - lo[1]) - slack, 0.0);
-    const double gz = dz == 0 ? 0.0 : fmax((dz < 0 ? lo[2] : r - lo[2]) - slack, 0.0);
-    if (gx * gx + gy * gy + gz * gz > rad2) continue;   // no point of that cell lies in the ball
-    const int2 se = cell_find(ix, pack_key(b, c[0] + dx, c[1] + dy, c[2] + dz));
-    for (int j = se.x; j < se.y; ++j) {
-      const int64_t t = ix.sidx[j];
-      const double ex = xyz[3 * t] - p[0], ey = xyz[3 * t + 1] - p[1], ez = xyz[3 * t + 2] - p[2];
-      if (sqrt(ex * ex + ey * ey + ez * ez) < radius) {
-        ++n;
-        m[0] += ex; m[1] += ey; m[2] += ez;
-        S[0] += ex * ex; S[1] += ex * ey; S[2] += ex * ez;
-        S[3] += ey * ey; S[4] += ey * ez; S[5] += ez * ez;
-      }
-    }
-  }
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t, double ex, double ey, double ez) {
+    ++n;
+    m[0] += ex; m[1] += ey; m[2] += ez;
+    S[0] += ex * ex; S[1] += ex * ey; S[2] += ex * ez;
+    S[3] += ey * ey; S[4] += ey * ez; S[5] += ez * ez;
+  });
   double nv[3] = {0.0, 0.0, 1.0};
   if (n >= 3) {
     const double inv = 1.0 / (double)n;

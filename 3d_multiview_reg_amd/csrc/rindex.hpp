@@ -44,6 +44,37 @@ __device__ __forceinline__ int2 cell_find(const RIndex& ix, uint64_t k) {
   }
 }
 
+// The walk of the ball of `radius` <= r around p over fragment b's points: the 27 cells around floor(p / r) through
+// the cell hash, without those whose box lies outside the ball (a lower bound of the distance to the box, shrunk by
+// slack = 1e-9 r, far above the rounding of p / r).  in_ball(t, ex, ey, ez) is called for every row t of the fragment
+// with sqrt(ex*ex + ey*ey + ez*ez) < radius (strict), e = x_t - p, in the order of the cells and of a cell's rows,
+// which follows the index alone.  Bounded: 27 cells, a cell's rows, the hash probe.
+template <class F>
+__device__ __forceinline__ void ball_walk(const RIndex& ix, const double* __restrict__ xyz, int b, const double (&p)[3],
+                                          double r, double radius, F&& in_ball) {
+  const double slack = 1e-9 * r, rad2 = radius * radius * (1.0 + 1e-9);
+  int64_t c[3];
+  double lo[3];   // distance to the lower neighbour cell along each axis; r - lo to the upper one
+  for (int e = 0; e < 3; ++e) {
+    const double cf = floor(p[e] / r);
+    c[e] = (int64_t)cf + OV_BIAS;
+    lo[e] = p[e] - cf * r;
+  }
+  for (int cell = 0; cell < 27; ++cell) {
+    const int dx = cell % 3 - 1, dy = (cell / 3) % 3 - 1, dz = cell / 9 - 1;
+    const double gx = dx == 0 ? 0.0 : fmax((dx < 0 ? lo[0] : r - lo[0]) - slack, 0.0);
+    const double gy = dy == 0 ? 0.0 : fmax((dy < 0 ? lo[1] : r - lo[1]) - slack, 0.0);
+    const double gz = dz == 0 ? 0.0 : fmax((dz < 0 ? lo[2] : r - lo[2]) - slack, 0.0);
+    if (gx * gx + gy * gy + gz * gz > rad2) continue;   // no point of that cell lies in the ball
+    const int2 se = cell_find(ix, pack_key(b, c[0] + dx, c[1] + dy, c[2] + dz));
+    for (int j = se.x; j < se.y; ++j) {
+      const int64_t t = ix.sidx[j];
+      const double ex = xyz[3 * t] - p[0], ey = xyz[3 * t + 1] - p[1], ez = xyz[3 * t + 2] - p[2];
+      if (sqrt(ex * ex + ey * ey + ez * ez) < radius) in_ball(t, ex, ey, ez);
+    }
+  }
+}
+
 inline char* take(char*& p, size_t b) {
   p = reinterpret_cast<char*>(((uintptr_t)p + 255) & ~(uintptr_t)255);
   char* r = p;

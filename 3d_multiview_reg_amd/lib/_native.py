@@ -121,6 +121,12 @@ _SIGS = {
     "mvr_compute_fpfh_workspace_bytes": (c_size, [c_i64]),
     "mvr_compute_fpfh": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_vp,
                                  c_vp, c_vp, c_size, c_vp]),
+    "mvr_knn_self_workspace_bytes": (c_size, [c_i64]),
+    "mvr_knn_self": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_int, c_vp, c_vp, c_vp, c_size,
+                             c_vp]),
+    "mvr_statistical_outlier": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
+    "mvr_radius_count": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_vp,
+                                 c_vp]),
     "mvr_feat_match": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "mvr_posegraph_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "mvr_posegraph_optimize": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int,

@@ -471,15 +471,48 @@ def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
     return pairs, init, viewpoints
 
 
+DENOISE_METHODS = {"statistical": {"nb_neighbors": 20, "std_ratio": 2.0}, "radius": {"nb_points": 16, "radius": None}}
+
+
+def _denoise_arguments(denoise, r=None):
+    """register_scene's checks of `denoise` that need no device (r: the index's cell size, where it is known) ->
+    None, or a dict of "method" and that method's options with the defaults filled in"""
+    from lib.overlap import _radius_outlier_arguments, _statistical_arguments
+    if denoise is None:
+        return None
+    if not isinstance(denoise, dict) or "method" not in denoise:
+        raise ValueError("register_scene: denoise must be None or a dict with a 'method'")
+    method = denoise["method"]
+    if method not in DENOISE_METHODS:
+        raise ValueError("register_scene: denoise method must be one of %s, not %r"
+                         % (", ".join(sorted(DENOISE_METHODS)), method))
+    unknown = sorted(set(denoise) - set(DENOISE_METHODS[method]) - {"method"})
+    if unknown:
+        raise ValueError("register_scene: denoise method %r has no option %s" % (method, ", ".join(map(repr, unknown))))
+    d = dict(DENOISE_METHODS[method], **denoise)
+    if method == "statistical":
+        d["nb_neighbors"], d["std_ratio"] = _statistical_arguments(d["nb_neighbors"], d["std_ratio"])
+    else:
+        rr = float("inf") if r is None else float(r)
+        d["nb_points"], radius = _radius_outlier_arguments(d["nb_points"], rr if d["radius"] is None else d["radius"],
+                                                           rr)
+        d["radius"] = None if d["radius"] is None else radius
+    return d
+
+
 def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=None, viewpoints=None, downsample=True,
                    dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
                    min_frags=1, min_points=1, ransac_checkers=False, line_process=False,
-                   preference_loop_closure=1.0):
+                   preference_loop_closure=1.0, denoise=None):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
          (downsample False: the points as given on the same index);
+      1b. denoise (None: nothing, the chain and the result as without it): {"method": "statistical", "nb_neighbors":
+         20, "std_ratio": 2.0} or {"method": "radius", "nb_points": 16, "radius": None} (options may be left out) —
+         fo.statistical_outliers / fo.radius_outliers per fragment, then fo = fo.select(keep): every later stage,
+         the fused scene included, sees the kept points only;
       2. estimate_normals(normal_radius, viewpoints) — viewpoints [n,3] in the fragments' own frames, None: their
          origins (where a range sensor stood);
       3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed` and
@@ -496,18 +529,30 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     pairs: a dict of numpy arrays over the pairs i < j (pairs [P,2], T_coarse [P,4,4], overlap [P], kept bool [P],
     T [P,4,4] the refined estimate (the coarse one where the pair was not kept), fitness and rmse [P] of the
     refinement, 0 where not kept; with line_process also pruned bool [P]: the pose graph dropped the pair), sync and
-    refined (the dicts of synchronize and optimize_pose_graph), fo, and scene (the dict of fuse_scene)."""
+    refined (the dicts of synchronize and optimize_pose_graph), fo, and scene (the dict of fuse_scene); with denoise
+    also denoise: keep (numpy bool over the points of step 1, fo.parent_rows are the kept ones) and removed [n] (the
+    points each fragment lost)."""
     from lib.fpfh import register_fpfh
     from lib.icp import gicp_refine, icp_refine, information_matrix
     from lib.overlap import FragmentOverlap
     n = len(xyz_list)
     pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints)
+    denoise = _denoise_arguments(denoise, 3.0 * float(voxel_size))
     threshold = OVERLAP_THRESHOLDS[dataset] if overlap_threshold is None else float(overlap_threshold)
     P = len(pairs)
     if downsample:
         fo = FragmentOverlap(xyz_list, "FCGF", voxel_size)
     else:
         fo = FragmentOverlap(xyz_list, "3DMatch", radius=3.0 * float(voxel_size))
+    denoised = None
+    if denoise is not None:
+        if denoise["method"] == "statistical":
+            keep = fo.statistical_outliers(denoise["nb_neighbors"], denoise["std_ratio"])["keep"]
+        else:
+            keep = fo.radius_outliers(denoise["nb_points"], denoise["radius"])["keep"]
+        sizes = np.diff(fo.off)
+        fo = fo.select(keep)
+        denoised = {"keep": keep.cpu().numpy(), "removed": (sizes - np.diff(fo.off)).astype(np.int64)}
     fo.estimate_normals(normal_radius, viewpoints)
     if init is None:
         fo.compute_fpfh(fpfh_radius)
@@ -546,5 +591,8 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
         pruned = np.zeros(P, dtype=bool)
         pruned[kept] = ~np.asarray(refined["kept"], dtype=bool)
         records["pruned"] = pruned
-    return {"R": R, "t": t, "poses": poses, "member": member, "pairs": records, "sync": sync, "refined": refined,
-            "fo": fo, "scene": scene}
+    result = {"R": R, "t": t, "poses": poses, "member": member, "pairs": records, "sync": sync, "refined": refined,
+              "fo": fo, "scene": scene}
+    if denoised is not None:
+        result["denoise"] = denoised
+    return result

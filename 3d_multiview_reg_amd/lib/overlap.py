@@ -27,6 +27,46 @@ def _radius(method, voxel_size):
     raise ValueError("Wrong overlap computation method was selected: %r" % (method,))
 
 
+MAX_KNN = 64   # the largest k of mvr_knn_self (include/mvreg.h)
+
+
+def _knn_arguments(k):
+    """knn's check that needs no device -> k"""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_KNN:
+        raise ValueError("knn: k must be an integer in [1, %d], not %r" % (MAX_KNN, k))
+    return int(k)
+
+
+def _statistical_arguments(nb_neighbors, std_ratio):
+    """statistical_outliers' checks that need no device -> (nb_neighbors, std_ratio)"""
+    if isinstance(nb_neighbors, bool) or int(nb_neighbors) != nb_neighbors or not 1 <= int(nb_neighbors) <= MAX_KNN:
+        raise ValueError("statistical_outliers: nb_neighbors must be an integer in [1, %d], not %r"
+                         % (MAX_KNN, nb_neighbors))
+    if not float(std_ratio) > 0.0:
+        raise ValueError("statistical_outliers: std_ratio must be positive, not %r" % (std_ratio,))
+    return int(nb_neighbors), float(std_ratio)
+
+
+def _radius_outlier_arguments(nb_points, radius, r):
+    """radius_outliers' checks that need no device, r the index's cell size -> (nb_points, radius)"""
+    if isinstance(nb_points, bool) or int(nb_points) != nb_points or int(nb_points) < 0:
+        raise ValueError("radius_outliers: nb_points must be a non-negative integer, not %r" % (nb_points,))
+    radius = float(r if radius is None else radius)
+    if not 0.0 < radius <= r:
+        raise ValueError("radius_outliers: radius %g must lie in (0, %g], the index's cell size (build the "
+                         "FragmentOverlap with radius >= it)" % (radius, r))
+    return int(nb_points), radius
+
+
+def _keep_mask(keep, M):
+    """select's check of its mask -> a bool tensor [M] (on whatever device keep was)"""
+    keep = torch.as_tensor(np.asarray(keep) if not torch.is_tensor(keep) else keep)
+    if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (M,):
+        raise ValueError("select: keep must be a bool / uint8 [%d], not %s %s"
+                         % (M, str(keep.dtype).replace("torch.", ""), list(keep.shape)))
+    return keep.bool()
+
+
 class FragmentOverlap(object):
     """Downsampled (method 'FCGF') or raw ('3DMatch') fragments of a scene with a radius index on the
     GPU.  xyz_list: list of [n_b, 3] arrays / tensors (any float dtype).  radius: the index's cell size and the
@@ -124,6 +164,74 @@ class FragmentOverlap(object):
                                    ws_b, N.stream()), "mvr_compute_fpfh")
         self.fpfh = fpfh
         return fpfh
+
+    def knn(self, k):
+        """The k nearest points of every point within its own fragment, the point itself among them (csrc/knn_self.hip
+        mvr_knn_self: Open3D's KDTreeFlann.search_knn_vector_3d on a fragment's own cloud, restated; exact).
+        -> (idx int32 [M,k], dist2 fp64 [M,k]) on the device, in the row order of fo.xyz: rows of fo.xyz ordered by
+        (squared distance, row); -1 / +inf beyond the fragment's size."""
+        k = _knn_arguments(k)
+        L = N.lib()
+        idx = torch.empty(self.M, k, dtype=torch.int32, device=self.device)
+        dist2 = torch.empty(self.M, k, dtype=torch.float64, device=self.device)
+        ws_b = L.mvr_knn_self_workspace_bytes(self.M)
+        ws = N.workspace(ws_b, self.device)
+        N.check(L.mvr_knn_self(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev), self.B,
+                               self.M, self.r, k, N.ptr(idx), N.ptr(dist2), N.ptr(ws), ws_b, N.stream()),
+                "mvr_knn_self")
+        return idx, dist2
+
+    def statistical_outliers(self, nb_neighbors=20, std_ratio=2.0):
+        """Open3D's remove_statistical_outlier(nb_neighbors, std_ratio) per fragment, restated (csrc/outlier.hip
+        mvr_statistical_outlier): a point is kept when the mean distance to its nb_neighbors nearest points (itself
+        among them, as in Open3D) lies below its fragment's mean + std_ratio standard deviations of that quantity.
+        Fragments of fewer than two points keep them.  -> {"keep": bool [M], "mean_dist": fp64 [M],
+        "threshold": fp64 [B]} on the device; fo.select(keep) applies it."""
+        k, std_ratio = _statistical_arguments(nb_neighbors, std_ratio)
+        _, dist2 = self.knn(k)
+        keep = torch.empty(self.M, dtype=torch.uint8, device=self.device)
+        mean_dist = torch.empty(self.M, dtype=torch.float64, device=self.device)
+        thr = torch.full((self.B,), float("inf"), dtype=torch.float64, device=self.device)
+        N.check(N.lib().mvr_statistical_outlier(N.ptr(dist2), N.ptr(self.off_dev), self.B, self.M, k, std_ratio,
+                                                N.ptr(keep), N.ptr(mean_dist), N.ptr(thr), N.stream()),
+                "mvr_statistical_outlier")
+        return {"keep": keep.bool(), "mean_dist": mean_dist, "threshold": thr}
+
+    def radius_outliers(self, nb_points=16, radius=None):
+        """Open3D's remove_radius_outlier(nb_points, radius) per fragment, restated (csrc/outlier.hip
+        mvr_radius_count): a point is kept when more than nb_points points of its fragment, itself among them, lie
+        closer than `radius` (None: fo.r; at most fo.r).  -> {"keep": bool [M], "count": int32 [M]} on the device."""
+        nb_points, radius = _radius_outlier_arguments(nb_points, radius, self.r)
+        count = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        N.check(N.lib().mvr_radius_count(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev),
+                                         self.B, self.M, self.r, radius, N.ptr(count), N.stream()),
+                "mvr_radius_count")
+        return {"keep": count > nb_points, "count": count}
+
+    def select(self, keep):
+        """A new FragmentOverlap over the rows with keep[i] (bool / uint8 [M], array or tensor), in their order: the
+        same method, voxel_size, r and device, `off` recomputed, the index rebuilt (no voxel pass), normals, n_nbr and
+        fpfh None since the neighbourhoods changed.  parent_rows (int64 [M'], device) maps its rows to this object's.
+        A fragment may become empty."""
+        keep = _keep_mask(keep, self.M).to(self.device)
+        rows = torch.nonzero(keep).reshape(-1)
+        kept_before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), keep.long().cumsum(0)])
+        off = kept_before.cpu().numpy()[self.off].astype(np.int64)
+        fo = object.__new__(FragmentOverlap)
+        fo.method, fo.voxel_size, fo.r, fo.device = self.method, self.voxel_size, self.r, self.device
+        fo.xyz = self.xyz[rows].contiguous()
+        fo.off = off
+        fo.B, fo.M = self.B, int(off[-1])
+        fo.off_dev = torch.from_numpy(off).to(self.device)
+        fo.max_points = int(np.max(np.diff(off))) if fo.B else 0
+        L = N.lib()
+        ib = L.mvr_radius_index_bytes(fo.M)
+        fo.index = torch.empty(ib, dtype=torch.uint8, device=self.device)
+        N.check(L.mvr_radius_index_build(N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(fo.index), ib,
+                                         N.stream()), "mvr_radius_index_build")
+        fo.normals = fo.n_nbr = fo.fpfh = None
+        fo.parent_rows = rows
+        return fo
 
     def counts(self, pairs, trans):
         """pairs [P, 2] fragment indices, trans [P, 4, 4] (the `trans` argument of the reference) ->

@@ -10,10 +10,12 @@ refinement and the fused cloud, all on the GPU.  Writes into --out
 --init traj.txt: a trajectory in that convention holding every pair i < j replaces the FPFH stage.
 --line_process: the pose-graph refinement runs with Open3D's line process and edge pruning (every pair that passed the
 gate is an uncertain edge); the pairs it pruned are counted in the printed line.
+--denoise statistical:20:2.0 | radius:16[:R]: Open3D's statistical / radius outlier removal on each fragment's centroids
+before anything else uses them; the points removed per fragment are printed.
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
            [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
-           [--checkers] [--line_process [--preference_loop_closure 1.0]]
+           [--checkers] [--line_process [--preference_loop_closure 1.0]] [--denoise statistical:20:2.0]
 """
 import argparse
 import os
@@ -45,6 +47,22 @@ def read_init(filename, n_fragments):
     return np.asarray([by_pair[p] for p in want], dtype=np.float64).reshape(-1, 4, 4)
 
 
+def parse_denoise(text):
+    """'statistical:NB:RATIO' or 'radius:NB[:R]' -> register_scene's denoise dict (ValueError on anything else)"""
+    parts = text.split(":")
+    try:
+        if parts[0] == "statistical" and len(parts) == 3:
+            d = {"method": "statistical", "nb_neighbors": int(parts[1]), "std_ratio": float(parts[2])}
+        elif parts[0] == "radius" and len(parts) in (2, 3):
+            d = {"method": "radius", "nb_points": int(parts[1]), "radius": float(parts[2]) if len(parts) == 3 else None}
+        else:
+            raise ValueError("neither form")
+    except ValueError:
+        raise ValueError("--denoise must be statistical:NB_NEIGHBORS:STD_RATIO or radius:NB_POINTS[:RADIUS], not %r"
+                         % (text,))
+    return d
+
+
 def parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--fragments", required=True, nargs="+", help="the fragments' PLY files (at least two)")
@@ -62,6 +80,10 @@ def parser():
     ap.add_argument("--line_process", action="store_true",
                     help="pose-graph refinement with the line process and edge pruning of Open3D's global_optimization")
     ap.add_argument("--preference_loop_closure", type=float, default=1.0, help="--line_process: Open3D's option")
+    ap.add_argument("--denoise", default=None, metavar="SPEC",
+                    help="remove outliers from the centroids before registration: statistical:20:2.0 (Open3D's "
+                         "remove_statistical_outlier(nb_neighbors, std_ratio)) or radius:16[:R] "
+                         "(remove_radius_outlier(nb_points, radius), R at most 3 voxel_size, its default)")
     return ap
 
 
@@ -76,6 +98,12 @@ def check_args(ap, a):
         ap.error("--anchor outside the fragments")
     if not a.preference_loop_closure > 0.0:
         ap.error("--preference_loop_closure must be positive")
+    if a.denoise is not None:
+        from lib.multiview import _denoise_arguments
+        try:
+            a.denoise = _denoise_arguments(parse_denoise(a.denoise), 3.0 * a.voxel_size)
+        except ValueError as e:
+            ap.error(str(e))
     return a
 
 
@@ -88,7 +116,8 @@ def main(argv=None):
     res = register_scene(frags, a.voxel_size, method=a.icp_method, init=init, dataset=a.dataset, seed=a.seed,
                          anchor=a.anchor, min_frags=a.min_frags, ransac_checkers=a.checkers,
                          **({} if not a.line_process else dict(line_process=True,
-                                                               preference_loop_closure=a.preference_loop_closure)))
+                                                               preference_loop_closure=a.preference_loop_closure)),
+                         **({} if a.denoise is None else dict(denoise=a.denoise)))
     ensure_dir(a.out)
     write_poses(res["poses"], os.path.join(a.out, "poses.txt"))
     rec = res["pairs"]
@@ -102,6 +131,9 @@ def main(argv=None):
           % (len(frags), int(rec["kept"].sum()), len(meta), int(np.asarray(res["member"]).sum()), a.anchor,
              float(res["refined"]["cost"][0]), float(res["refined"]["cost"][1]), len(scene["xyz"]), a.voxel_size,
              a.out))
+    if a.denoise is not None:
+        print("denoise (%s): points removed per fragment: %s"
+              % (a.denoise["method"], " ".join(str(int(v)) for v in res["denoise"]["removed"])))
     if a.line_process:
         print("line process: %d of the %d gated pairs pruned" % (int(rec["pruned"].sum()), int(rec["kept"].sum())))
     return res

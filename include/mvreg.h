@@ -345,7 +345,8 @@ int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
  * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane,
- * mvr_icp_refine_generalized and mvr_compute_fpfh calls on the same points.  B < 32768.
+ * mvr_icp_refine_generalized, mvr_compute_fpfh, mvr_knn_self and mvr_radius_count calls on the same points.
+ * B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
  * cells of a fragment form one run of the sorted order under one hash entry, a query walks the whole run, and
@@ -539,6 +540,59 @@ size_t mvr_compute_fpfh_workspace_bytes(int64_t M);
 int mvr_compute_fpfh(const void* index, size_t index_bytes, const double* xyz, const double* normals,
                      const int64_t* off, int B, int64_t M, double r_index, double radius, float* fpfh,
                      float* spfh_out, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Exact k nearest neighbours of every point within its own fragment, on a radius index (csrc/knn_self.hip;
+ * DESIGN.md 4.21a): Open3D's KDTreeFlann.search_knn_vector_3d on the cloud the tree was built on, restated from the
+ * maths; Open3D parity is unpinned.  tests/knn_oracle.py is the numpy restatement.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`.
+ *   Candidates of point i: every point j of its own fragment, i itself included.
+ *   d2(i, j) = (ex*ex + ey*ey) + ez*ez, e = x_j - x_i, in fp64 with every product and sum rounded on its own (no
+ *   FMA), so a host restatement reproduces dist2 bit for bit.
+ *   Row i of idx [M,k] / dist2 [M,k] holds the min(k, n_b) smallest candidates ordered by (d2, row) lexicographically:
+ *   on equal distances the lower row first, so with exact duplicates a point need not be its own first neighbour.
+ *   idx are rows of xyz (global, not fragment-local).  The remaining entries are idx = -1, dist2 = +inf.  Every one
+ *   of the M k entries is written and nothing beyond them; rows are in the row order of xyz.  (A candidate whose d2
+ *   is NaN is never returned.)
+ *   The search is exact for any input and any r_index: r_index only decides the cost.  One thread per point walks the
+ *   cells around it ring by ring (2 rings); a point whose k-th neighbour is not certain by then is resolved by a
+ *   second launch that scans its fragment's rows, n_b distance evaluations.  A point's outputs are a function of its
+ *   fragment alone: bit-identical whatever other fragments are in the batch (apart from the row offset in idx) and
+ *   from run to run.  No host synchronisation.  After the call the first int32 of `workspace`
+ *   (>= mvr_knn_self_workspace_bytes(M)) holds the number of points the second launch resolved (a diagnostic).
+ *   MVR_EINVAL, scalars first: negative M or M >= 2^31; B <= 0 or B >= 32768; r_index <= 0; k < 1 or k > 64.
+ *   M == 0 then returns MVR_OK.  With M > 0: a NULL index, xyz, off, idx, dist2 or workspace,
+ *   index_bytes < mvr_radius_index_bytes(M), or workspace_bytes < mvr_knn_self_workspace_bytes(M).
+ * ---------------------------------------------------------------------- */
+size_t mvr_knn_self_workspace_bytes(int64_t M);
+int mvr_knn_self(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
+                 double r_index, int k, int32_t* idx, double* dist2, void* workspace, size_t workspace_bytes,
+                 mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Outlier statistics of a fragment's own points (csrc/outlier.hip): what Open3D's
+ * remove_statistical_outlier(nb_neighbors, std_ratio) and remove_radius_outlier(nb_points, radius) decide on, each
+ * fragment its own cloud as when Open3D is called per fragment, restated from the maths; Open3D parity is unpinned.
+ * mvr_statistical_outlier: dist2 [M,k] is the output of mvr_knn_self with k = nb_neighbors (the point itself counts
+ *   among them, as in Open3D).  mean_i = (sum over the found entries, in ascending slot order, of sqrt(dist2[i,s]))
+ *   / min(k, n_b); per fragment b: mu_b = mean of mean_i, sd_b = sqrt(sum (mean_i - mu_b)^2 / (n_b - 1)),
+ *   thr_b = mu_b + std_ratio sd_b, keep_i = mean_i < thr_b (strict).  A fragment with n_b < 2 keeps all its points
+ *   and has thr_b = +inf (Open3D divides by zero there).  Outputs keep [M] (0 / 1), mean_dist [M], thr [B].
+ *   One workgroup per fragment, sums in a fixed order through a fixed tree: bit-identical from run to run, and a
+ *   fragment's outputs do not depend on the batch around it.
+ *   MVR_EINVAL, scalars first: negative M or M >= 2^31; B <= 0 or B >= 32768; k < 1 or k > 64; std_ratio <= 0.
+ *   M == 0 then returns MVR_OK with nothing written (thr neither).  With M > 0: a NULL dist2, off, keep, mean_dist
+ *   or thr.
+ * mvr_radius_count: count[i] = the number of points of i's fragment with sqrt(ex*ex + ey*ey + ez*ez) < radius,
+ *   e = x_j - x_i: the expression, the strictness and the inclusion of the point itself of mvr_estimate_normals'
+ *   n_nbr (one walk, csrc/rindex.hpp).  Open3D keeps a point when count > nb_points.
+ *   MVR_EINVAL, scalars first: the rules of mvr_estimate_normals (radius > r_index among them).  M == 0 then returns
+ *   MVR_OK.  With M > 0: a NULL index, xyz, off or count, or index_bytes < mvr_radius_index_bytes(M).
+ * ---------------------------------------------------------------------- */
+int mvr_statistical_outlier(const double* dist2, const int64_t* off, int B, int64_t M, int k, double std_ratio,
+                            uint8_t* keep, double* mean_dist, double* thr, mvr_stream_t stream);
+int mvr_radius_count(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
+                     double r_index, double radius, int32_t* count, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Nearest neighbour in feature space between ragged fragments (csrc/feat_match.hip), for any channel
