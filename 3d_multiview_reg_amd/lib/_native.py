@@ -58,6 +58,10 @@ _SIGS = {
     "mvr_ransac_checked": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_int, c_int, ctypes.c_double, ctypes.c_uint64,
                                    c_int, ctypes.c_double, ctypes.c_double, c_vp, c_vp, ctypes.c_double, c_vp, c_vp,
                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "mvr_fgr_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "mvr_fgr": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, ctypes.c_double, c_int, ctypes.c_double, c_int, c_int,
+                        ctypes.c_double, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size,
+                        c_vp]),
     "mvr_sync_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "mvr_sync_poses": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
                                ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

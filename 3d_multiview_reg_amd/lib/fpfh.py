@@ -1,6 +1,7 @@
 """Weights-free global registration: FPFH descriptors (csrc/fpfh.hip mvr_compute_fpfh, FragmentOverlap.compute_fpfh),
 nearest neighbours in feature space (csrc/feat_match.hip mvr_feat_match) and the batched RANSAC (mvr_ransac,
-lib.utils.run_ransac_batch); DESIGN.md 4.24, the semantics are in include/mvreg.h.
+lib.utils.run_ransac_batch) or Fast Global Registration (mvr_fgr, lib.utils.run_fgr_batch; register_fgr, DESIGN.md
+4.28); DESIGN.md 4.24, the semantics are in include/mvreg.h.
 
 What Open3D users write as compute_fpfh_feature + registration_ransac_based_on_feature_matching, for every pair of a
 scene at once and without a pretrained network: a coarse estimate that feeds lib.icp.icp_refine / gicp_refine and
@@ -11,7 +12,7 @@ import numpy as np
 import torch
 
 from lib import _native as N
-from lib.utils import RANSAC_DIST, RANSAC_ITERS, RANSAC_N, run_ransac_batch, run_ransac_checked_batch
+from lib.utils import RANSAC_DIST, RANSAC_ITERS, RANSAC_N, run_fgr_batch, run_ransac_batch, run_ransac_checked_batch
 
 MAX_CHANNELS = 64
 
@@ -121,6 +122,31 @@ def register_fpfh(fo, pairs, mutual=True, seed=0, ransac_n=RANSAC_N, max_dist=RA
     T, fit, rmse, _ = run_ransac_batch(xyz_s, xyz_t, counts, seed=seed, ransac_n=ransac_n, max_dist=max_dist,
                                        iters=iters, device=fo.device, return_all=True)
     return {"T": T, "fitness": fit, "rmse": rmse, "n_matches": counts}
+
+
+def register_fgr(fo, pairs, mutual=True, seed=0, **fgr_options):
+    """register_fpfh with Fast Global Registration (lib.utils.run_fgr_batch, csrc/fgr.hip mvr_fgr) in place of RANSAC:
+    match_features, correspondences, then the graduated non-convexity over each pair's matches; fgr_options are
+    run_fgr_batch's (max_dist, iters, division_factor, tuple_test, tuple_scale, max_tuples, tuple_factor), `seed`
+    keys the tuple filter's draws.  No hypotheses are sampled, so it needs matches whose inlier share is tens of
+    percent (FCGF descriptors' mutual matches, near-complete overlap); on FPFH matches of partly overlapping
+    fragments the checked RANSAC of register_fpfh stays the choice.
+    -> register_fpfh's keys (T, fitness, rmse, n_matches) plus n_used, n_tuples and status int32 [P]; pairs without
+    matches get the identity (status 1)."""
+    if getattr(fo, "fpfh", None) is None:
+        raise ValueError("register_fgr: needs fo.fpfh (call fo.compute_fpfh())")
+    if set(fgr_options) & {"counts", "device", "return_trace"}:
+        raise ValueError("register_fgr: counts, device and return_trace are not options")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    matches = match_features(fo.fpfh, fo.off, pairs, mutual)
+    counts = np.array([len(m) for m in matches], dtype=np.int64)
+    xyz_s, xyz_t = correspondences(fo, pairs, matches)
+    if len(pairs) == 0:
+        return {"T": np.zeros((0, 4, 4)), "fitness": np.zeros(0), "rmse": np.zeros(0), "n_matches": counts,
+                "n_used": np.zeros(0, np.int32), "n_tuples": np.zeros(0, np.int32), "status": np.zeros(0, np.int32)}
+    out = run_fgr_batch(xyz_s, xyz_t, counts, seed=seed, device=fo.device, **fgr_options)
+    return {"T": out["T"], "fitness": out["fitness"], "rmse": out["rmse"], "n_matches": counts,
+            "n_used": out["n_used"], "n_tuples": out["n_tuples"], "status": out["status"]}
 
 
 def correspondences(fo, pairs, matches, rows=None):

@@ -471,6 +471,7 @@ def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
     return pairs, init, viewpoints
 
 
+COARSE_METHODS = ("ransac", "fgr")   # register_scene's step 4: lib.fpfh.register_fpfh / register_fgr
 DENOISE_METHODS = {"statistical": {"nb_neighbors": 20, "std_ratio": 2.0}, "radius": {"nb_points": 16, "radius": None}}
 
 
@@ -504,7 +505,7 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
                    dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
                    min_frags=1, min_points=1, ransac_checkers=False, line_process=False,
-                   preference_loop_closure=1.0, denoise=None):
+                   preference_loop_closure=1.0, denoise=None, coarse="ransac"):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
@@ -516,7 +517,9 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
       2. estimate_normals(normal_radius, viewpoints) — viewpoints [n,3] in the fragments' own frames, None: their
          origins (where a range sensor stood);
       3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed` and
-         checkers=ransac_checkers (True or a dict: RANSAC with correspondence checkers and 100000 draws)
+         checkers=ransac_checkers (True or a dict: RANSAC with correspondence checkers and 100000 draws), or with
+         coarse="fgr" lib.fpfh.register_fgr (Fast Global Registration, `seed` keying its tuple filter; not with
+         ransac_checkers.  It wants matches with tens of percent inliers: RANSAC stays the default)
          (init [P,4,4], x_j ~ T x_i for the pairs i < j in that order, replaces 3 and 4);
       5. the overlap gate of the pairwise benchmark: a pair is kept when FragmentOverlap.ratios >= overlap_threshold
          (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
@@ -532,10 +535,14 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     refined (the dicts of synchronize and optimize_pose_graph), fo, and scene (the dict of fuse_scene); with denoise
     also denoise: keep (numpy bool over the points of step 1, fo.parent_rows are the kept ones) and removed [n] (the
     points each fragment lost)."""
-    from lib.fpfh import register_fpfh
+    from lib.fpfh import register_fgr, register_fpfh
     from lib.icp import gicp_refine, icp_refine, information_matrix
     from lib.overlap import FragmentOverlap
     n = len(xyz_list)
+    if coarse not in COARSE_METHODS:
+        raise ValueError("register_scene: coarse must be one of %s, not %r" % (", ".join(COARSE_METHODS), coarse))
+    if coarse == "fgr" and ransac_checkers is not False:
+        raise ValueError("register_scene: ransac_checkers belongs to coarse='ransac', not to coarse='fgr'")
     pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints)
     denoise = _denoise_arguments(denoise, 3.0 * float(voxel_size))
     threshold = OVERLAP_THRESHOLDS[dataset] if overlap_threshold is None else float(overlap_threshold)
@@ -556,7 +563,11 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     fo.estimate_normals(normal_radius, viewpoints)
     if init is None:
         fo.compute_fpfh(fpfh_radius)
-        T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed, checkers=ransac_checkers)["T"], dtype=np.float64)
+        if coarse == "fgr":
+            T_coarse = np.asarray(register_fgr(fo, pairs, seed=seed)["T"], dtype=np.float64)
+        else:
+            T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed, checkers=ransac_checkers)["T"],
+                                  dtype=np.float64)
     else:
         T_coarse = init
     overlap = fo.ratios(pairs, np.linalg.inv(T_coarse))      # the gate's `trans` is the inverse of the estimate

@@ -445,6 +445,71 @@ def run_ransac_checked_batch(xyz_i, xyz_j, counts=None, seed=0, ransac_n=3, max_
             "best_iter": best.cpu().numpy(), "n_pass": n_pass.cpu().numpy(), "n_valid": n_valid.cpu().numpy()}
 
 
+def run_fgr_batch(xyz_i, xyz_j, counts=None, seed=0, max_dist=RANSAC_DIST, iters=64, division_factor=1.4,
+                  tuple_test=True, tuple_scale=0.95, max_tuples=1000, tuple_factor=100, device=None,
+                  return_trace=False):
+    """Batched Fast Global Registration over correspondences (csrc/fgr.hip mvr_fgr; Zhou, Park, Koltun 2016, the
+    defaults of Open3D's FastGlobalRegistrationOption with max_dist in the clouds' own units): graduated
+    non-convexity over the rows the tuple filter keeps (tuple_test: of tuple_factor * n tests of three drawn rows,
+    the first max_tuples whose three edges agree in length within tuple_scale; False: every row).  xyz_i, xyz_j,
+    counts, seed as run_ransac_batch (the same draw stream).  No hypotheses are sampled: it wants matches whose
+    inlier share is tens of percent.  With the filter on, mvr_fgr is given min(max_tuples,
+    tuple_factor * n) as its cap: no pair has more tests than that, so the result is the same and the workspace
+    (3 rows per tuple of the cap) smaller.
+    Returns a dict of numpy arrays: T [P,4,4] fp64 (x_j ~ T x_i), fitness, rmse [P] (over all rows at max_dist),
+    n_used, n_tuples, status int32 [P] (bits as lib.icp: 1 too few rows, 4 a non-finite coordinate, 8 a degenerate
+    system; 1 and 4 give the identity) and, with return_trace, trace [P,iters,2] (mu and the mean weighted squared
+    residual of every iteration, -1 after an early end)."""
+    from lib import _native as N
+    max_dist, division_factor, tuple_scale = float(max_dist), float(division_factor), float(tuple_scale)
+    iters, max_tuples = int(iters), int(max_tuples)
+    tuple_factor = int(tuple_factor) if tuple_test else 0
+    if not (max_dist > 0.0 and np.isfinite(max_dist)):
+        raise ValueError("max_dist must be positive and finite")
+    if iters < 0:
+        raise ValueError("iters must be at least 0")
+    if not (np.isfinite(division_factor) and division_factor > 1.0):
+        raise ValueError("division_factor must be finite and above 1")
+    if max_tuples < 1:
+        raise ValueError("max_tuples must be at least 1")
+    if tuple_test and tuple_factor < 1:
+        raise ValueError("tuple_factor must be at least 1 (tuple_test=False turns the filter off)")
+    if tuple_test and not 0.0 < tuple_scale <= 1.0:
+        raise ValueError("tuple_scale must be in (0, 1]")
+    shape = tuple(np.shape(xyz_i))
+    if len(shape) != 3 or shape != tuple(np.shape(xyz_j)) or shape[-1] != 3:
+        raise ValueError("xyz_i / xyz_j must both be [P, n, 3]")
+    P, n = shape[0], shape[1]
+    if tuple_factor * n >= 1 << 31:
+        raise ValueError("tuple_factor * n must stay below 2^31")
+    cnt = torch.full((P,), n, dtype=torch.int32) if counts is None else torch.as_tensor(counts).to(torch.int32)
+    if cnt.numel() != P or bool((cnt < 0).any()) or bool((cnt > n).any()):
+        raise ValueError("counts must be [P] with 0 <= counts <= n")
+    N.require_hip()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    x1 = torch.as_tensor(xyz_i).to(dev, torch.float64).contiguous()
+    x2 = torch.as_tensor(xyz_j).to(dev, torch.float64).contiguous()
+    cnt = cnt.to(dev)
+    if tuple_factor:
+        max_tuples = min(max_tuples, max(tuple_factor * n, 1))   # no pair has more tests: a smaller workspace
+    T = torch.empty(P, 4, 4, dtype=torch.float64, device=dev)
+    fit = torch.empty(P, dtype=torch.float64, device=dev)
+    rmse = torch.empty(P, dtype=torch.float64, device=dev)
+    n_used, n_tuples, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    trace = torch.empty(P, iters, 2, dtype=torch.float64, device=dev) if return_trace else None
+    L = N.lib()
+    ws = N.workspace(L.mvr_fgr_workspace_bytes(P, n, max_tuples), dev)
+    N.check(L.mvr_fgr(N.ptr(x1), N.ptr(x2), n * 3, N.ptr(cnt), P, max_dist, iters, division_factor, tuple_factor,
+                      max_tuples, tuple_scale, int(seed) & 0xFFFFFFFFFFFFFFFF, N.ptr(T), N.ptr(fit), N.ptr(rmse),
+                      N.ptr(n_used), N.ptr(n_tuples), N.ptr(status), N.ptr(trace), N.ptr(ws), ws.numel(), N.stream()),
+            "mvr_fgr")
+    out = {"T": T.cpu().numpy(), "fitness": fit.cpu().numpy(), "rmse": rmse.cpu().numpy(),
+           "n_used": n_used.cpu().numpy(), "n_tuples": n_tuples.cpu().numpy(), "status": status.cpu().numpy()}
+    if return_trace:
+        out["trace"] = trace.cpu().numpy()
+    return out
+
+
 def run_ransac(xyz_i, xyz_j, seed=0):
     """utils.py:671-709: RANSAC-based estimate of the transformation mapping xyz_i [n,3] onto xyz_j [n,3]
     (correspondences are row-aligned), returned as a 4x4 float64 array.  Open3D seeds its draws from the

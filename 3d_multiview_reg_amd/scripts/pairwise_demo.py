@@ -12,8 +12,9 @@ usage: python -m scripts.pairwise_demo configs/pairwise_registration/demo/config
 
 --fpfh registers the pair without any network or checkpoint (lib/fpfh.py): voxel centroids at the
 config's voxel_size, normals oriented to each cloud's mean, FPFH descriptors, mutual feature matches, RANSAC and,
-with --icp, a point-to-point ICP refinement; T is printed and written to the same est_T.log.
-    [--fpfh [--fpfh_radius R] [--normal_radius R] [--icp]]   (defaults: 5 and 2 voxel sizes)
+with --icp, a point-to-point ICP refinement; T is printed and written to the same est_T.log.  --fpfh --fgr runs Fast
+Global Registration (lib.fpfh.register_fgr) on the matches in place of RANSAC.
+    [--fpfh [--fpfh_radius R] [--normal_radius R] [--checkers | --fgr] [--icp]]   (defaults: 5 and 2 voxel sizes)
 """
 import argparse
 import logging
@@ -55,8 +56,8 @@ def _write(est_T, args):
 
 
 def main_fpfh(cfg, args, logger=logging.getLogger()):
-    """--fpfh: FPFH + RANSAC (+ ICP) on the two clouds' voxel centroids; no model, no checkpoint"""
-    from lib.fpfh import register_fpfh
+    """--fpfh: FPFH + RANSAC or FGR (+ ICP) on the two clouds' voxel centroids; no model, no checkpoint"""
+    from lib.fpfh import register_fgr, register_fpfh
     from lib.icp import icp_refine
     from lib.overlap import FragmentOverlap
     voxel = float(cfg["misc"]["voxel_size"])
@@ -70,12 +71,19 @@ def main_fpfh(cfg, args, logger=logging.getLogger()):
     xyz = fo.xyz.cpu().numpy()
     fo.estimate_normals(r_normal, viewpoints=[xyz[fo.off[b]:fo.off[b + 1]].mean(0) for b in range(2)])
     fo.compute_fpfh(r_fpfh)
-    out = register_fpfh(fo, [[0, 1]], checkers=bool(getattr(args, "checkers", False)))
+    fgr = bool(getattr(args, "fgr", False))
+    if fgr:
+        out = register_fgr(fo, [[0, 1]])
+    else:
+        out = register_fpfh(fo, [[0, 1]], checkers=bool(getattr(args, "checkers", False)))
     if "n_pass" in out:
         logger.info("checkers: %d of 100000 samples passed, %d scored", out["n_pass"][0], out["n_valid"][0])
     est_T = out["T"][0]
-    logger.info("FPFH + RANSAC: %d mutual matches of %d / %d points, fitness %.4f, rmse %.4f", out["n_matches"][0],
-                fo.off[1], fo.off[2] - fo.off[1], out["fitness"][0], out["rmse"][0])
+    logger.info("FPFH + %s: %d mutual matches of %d / %d points, fitness %.4f, rmse %.4f", "FGR" if fgr else "RANSAC",
+                out["n_matches"][0], fo.off[1], fo.off[2] - fo.off[1], out["fitness"][0], out["rmse"][0])
+    if fgr:
+        print("FGR: fitness %.4f, rmse %.4f over %d mutual matches (%d tuples, status %d)"
+              % (out["fitness"][0], out["rmse"][0], out["n_matches"][0], out["n_tuples"][0], out["status"][0]))
     if args.icp:
         ref = icp_refine(fo, [[0, 1]], est_T[None], max_dist=min(fo.r, 2.0 * voxel))
         est_T = ref["T"][0]
@@ -88,7 +96,18 @@ def main_fpfh(cfg, args, logger=logging.getLogger()):
     return est_T
 
 
+def check_args(args):
+    """ValueError for --fgr without --fpfh or with --checkers"""
+    if getattr(args, "fgr", False):
+        if not getattr(args, "fpfh", False):
+            raise ValueError("--fgr registers the FPFH matches: it needs --fpfh")
+        if getattr(args, "checkers", False):
+            raise ValueError("--checkers belongs to RANSAC: not with --fgr")
+    return args
+
+
 def main(cfg, args, logger=logging.getLogger()):
+    check_args(args)
     if getattr(args, "fpfh", False):
         return main_fpfh(cfg, args, logger)
     np.random.seed(41)     # pairwise_demo.py:25-28 (the Sampler draws on numpy's global RandomState)
@@ -142,6 +161,8 @@ def parser():
     ap.add_argument("--normal_radius", default=None, type=float, help="Normal radius (default 2 voxel sizes).")
     ap.add_argument("--checkers", action="store_true",
                     help="With --fpfh: RANSAC with edge-length and distance checkers, 3-point samples, 100000 draws.")
+    ap.add_argument("--fgr", action="store_true",
+                    help="With --fpfh: Fast Global Registration on the matches instead of RANSAC (not with --checkers).")
     ap.add_argument("--icp", action="store_true", help="With --fpfh: refine the estimate by point-to-point ICP.")
     return ap
 

@@ -15,7 +15,7 @@ before anything else uses them; the points removed per fragment are printed.
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
            [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
-           [--checkers] [--line_process [--preference_loop_closure 1.0]] [--denoise statistical:20:2.0]
+           [--checkers | --coarse fgr] [--line_process [--preference_loop_closure 1.0]] [--denoise statistical:20:2.0]
 """
 import argparse
 import os
@@ -33,6 +33,7 @@ from scripts.multiview_sync import write_poses  # noqa: E402
 
 ICP_METHODS = ("point_to_point", "point_to_plane", "generalized")   # lib.multiview.ICP_METHODS
 DATASETS = ("3d_match", "redwood")                                  # lib.multiview.OVERLAP_THRESHOLDS
+COARSE_METHODS = ("ransac", "fgr")                                  # lib.multiview.COARSE_METHODS
 
 
 def read_init(filename, n_fragments):
@@ -77,6 +78,9 @@ def parser():
     ap.add_argument("--seed", type=int, default=0, help="RANSAC draw stream seed")
     ap.add_argument("--checkers", action="store_true",
                     help="RANSAC with the edge-length and distance checkers: 3-point samples, 100000 draws")
+    ap.add_argument("--coarse", default="ransac", choices=COARSE_METHODS,
+                    help="the coarse estimate from the FPFH matches: RANSAC, or Fast Global Registration (for matches "
+                         "with tens of percent inliers; not with --checkers)")
     ap.add_argument("--line_process", action="store_true",
                     help="pose-graph refinement with the line process and edge pruning of Open3D's global_optimization")
     ap.add_argument("--preference_loop_closure", type=float, default=1.0, help="--line_process: Open3D's option")
@@ -96,6 +100,8 @@ def check_args(ap, a):
         ap.error("--min_frags must be at least 1")
     if not 0 <= a.anchor < len(a.fragments):
         ap.error("--anchor outside the fragments")
+    if a.coarse == "fgr" and a.checkers:
+        ap.error("--checkers belongs to --coarse ransac")
     if not a.preference_loop_closure > 0.0:
         ap.error("--preference_loop_closure must be positive")
     if a.denoise is not None:
@@ -115,6 +121,7 @@ def main(argv=None):
     init = None if a.init is None else read_init(a.init, len(frags))
     res = register_scene(frags, a.voxel_size, method=a.icp_method, init=init, dataset=a.dataset, seed=a.seed,
                          anchor=a.anchor, min_frags=a.min_frags, ransac_checkers=a.checkers,
+                         **({} if a.coarse == "ransac" else dict(coarse=a.coarse)),
                          **({} if not a.line_process else dict(line_process=True,
                                                                preference_loop_closure=a.preference_loop_closure)),
                          **({} if a.denoise is None else dict(denoise=a.denoise)))

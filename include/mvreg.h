@@ -136,6 +136,49 @@ int mvr_ransac_checked(const double* x1, const double* x2, int64_t x_pstride, co
                        size_t workspace_bytes, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Fast Global Registration over given correspondences, batched over pairs (csrc/fgr.hip).
+ * Zhou, Park, Koltun, ECCV 2016: what Open3D offers as registration_fgr_based_on_feature_matching, restated from the
+ * maths (Open3D bit parity is not a goal).  It replaces nothing in the reference.  No hypotheses are sampled: a
+ * Geman-McClure cost over the correspondences is minimised by Gauss-Newton steps while its scale shrinks.
+ *   x1, x2, x_pstride, n, P and the draws: as mvr_ransac (x2 ~ T x1, n[p] valid rows of pair p);
+ *   n_max = x_pstride / 3 bounds every n[p].  All geometry is fp64.  Pair p, in four steps:
+ *   A. Tuple filter (tuple_factor > 0).  Test it = 0 .. tuple_factor * n[p] - 1 draws three rows, draw j being
+ *      splitmix64(seed + ((p<<40)|(it<<8)|j) * 0x9E3779B97F4A7C15) % n[p].  It passes when the rows are distinct and
+ *      every pair of them has ls2 >= s2 * lt2 and lt2 >= s2 * ls2 (check 2 of mvr_ransac_checked with
+ *      s2 = tuple_scale * tuple_scale: rounded fp64 operations, no fma, so the set of passing tests is exact).  The
+ *      first max_tuples passing tests in ascending `it` give the used rows: three per tuple in draw order, repeats
+ *      across tuples kept.  n_tuples[p] of them, n_used[p] = 3 n_tuples[p].  tuple_factor == 0: the used rows are all
+ *      n[p] rows, n_tuples[p] = 0, n_used[p] = n[p].
+ *   B. Normalisation over all n[p] rows: mu1, mu2 the means of x1, x2, scale the largest |x1_i - mu1|, |x2_i - mu2|,
+ *      p = (x1 - mu1) / scale, q = (x2 - mu2) / scale, delta = max_dist / scale.
+ *   C. From R = I, t = 0, mu = 1, for k = 0 .. iters - 1: if k % 4 == 0 and mu > delta^2, mu <- mu / division_factor
+ *      (not clamped); over the used rows p' = R p + t, e = p' - q, w = (mu / (|e|^2 + mu))^2; H = sum w J^T J,
+ *      g = sum w J^T e with J = [-[p']x | I]; xi = -H^-1 g by Cholesky, a pivot not above 1e-12 of the largest
+ *      diagonal entry ends the loop with status bit 8 and T kept; T <- D T, D = [Rz(xi2) Ry(xi1) Rx(xi0) | xi[3:6]].
+ *   D. T [P,4,4] row-major = [R | scale t + mu2 - R mu1]; fitness [P], rmse [P] over all n[p] rows at max_dist as
+ *      mvr_ransac scores a hypothesis (d2 < max_dist^2, inliers / n[p], sqrt(sum d2 / inliers), 0 without inliers).
+ *      iters == 0 gives the loop's start in the clouds' units, R = I and t = mu2 - mu1 (the centroids aligned, not the
+ *      4 x 4 identity), scored the same way; status 0.
+ *   trace (NULL: not exported) [P,iters,2]: row k holds the mu of iteration k and the mean of w |e|^2 over the used
+ *   rows at the T the iteration started from; the rows after the iteration that ended the loop early hold -1.
+ *   status [P], the bits of lib/icp.py: 1 few (n[p] < 3, fewer than 3 used rows, scale 0), 4 invalid (a coordinate
+ *   among the n[p] rows is not finite, or n[p] outside [0, n_max]), 8 degenerate (step C).  A pair with bit 1 or 4
+ *   gets T = identity, fitness = rmse = 0, n_used = n_tuples = 0 and a trace of -1.
+ *   One workgroup per pair, one launch, no atomics, every sum in a fixed order: two runs give the same bytes.
+ *   workspace (8-byte aligned) >= mvr_fgr_workspace_bytes(P, n_max, max_tuples): max(n_max, 3 max_tuples) rows of 6
+ *   doubles per pair.
+ *   MVR_EINVAL: P < 0 or >= 2^23, iters < 0, max_dist not positive and finite, division_factor not finite or <= 1,
+ *   tuple_factor < 0, tuple_scale outside (0, 1] with tuple_factor > 0, max_tuples < 1, x_pstride < 0,
+ *   tuple_factor * n_max >= 2^31, a short workspace and, with P > 0, a NULL x1, x2, n, T, fitness, rmse, n_used,
+ *   n_tuples, status or workspace.
+ * ---------------------------------------------------------------------- */
+size_t mvr_fgr_workspace_bytes(int P, int n_max, int max_tuples);
+int mvr_fgr(const double* x1, const double* x2, int64_t x_pstride, const int32_t* n, int P, double max_dist,
+            int iters, double division_factor, int tuple_factor, int max_tuples, double tuple_scale, uint64_t seed,
+            double* T, double* fitness, double* rmse, int32_t* n_used, int32_t* n_tuples, int32_t* status,
+            double* trace, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Multiview pose synchronisation, batched over scenes (csrc/sync.hip).
  * The closed-form weighted solve of the paper's sections 3.2-3.3 with optional IRLS; the reference never released
  * this stage (its README.md:116), so it replaces nothing: it turns the pairwise estimates of a scene into one pose
