@@ -9,6 +9,7 @@
 // Coordinates are taken relative to the point: the covariance cancels at the size of the ball, not of the scene.
 // Every loop is bounded: 27 cells, a cell's rows, the Jacobi sweep cap, and the hash probe (cap >= 2 M).
 #include "common.hpp"
+#include "cov3.hpp"
 #include "rindex.hpp"
 #include "mvreg.h"
 #include <math.h>
@@ -22,44 +23,6 @@ namespace mvr {
 #endif
 constexpr int kNormalsThreads = MVR_NORMALS_THREADS;
 
-// One Jacobi rotation of the symmetric a that zeroes a[P][Q]; R is the third index.  V <- V J.
-template <int P, int Q, int R>
-__device__ __forceinline__ void sym_rotate(double (&a)[3][3], double (&V)[3][3]) {
-  const double apq = a[P][Q];
-  if (apq == 0.0 || fabs(apq) <= 1e-17 * (fabs(a[P][P]) + fabs(a[Q][Q]))) return;
-  const double th = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-  const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(1.0 + th * th));
-  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-  a[P][P] -= t * apq;
-  a[Q][Q] += t * apq;
-  a[P][Q] = a[Q][P] = 0.0;
-  const double arp = a[R][P], arq = a[R][Q];
-  a[R][P] = a[P][R] = c * arp - s * arq;
-  a[R][Q] = a[Q][R] = s * arp + c * arq;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double vp = V[i][P], vq = V[i][Q];
-    V[i][P] = c * vp - s * vq;
-    V[i][Q] = s * vp + c * vq;
-  }
-}
-
-// The symmetric (two-sided) form of svd3.hpp's cyclic Jacobi: eigenvalues on the diagonal of a, eigenvectors in the
-// columns of V.  Zero off-diagonals are left alone, so a zero row and column keep their axis exactly.
-__device__ __forceinline__ void jacobi_eig3(double (&a)[3][3], double (&V)[3][3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-    if (!(off > 1e-17 * (fabs(a[0][0]) + fabs(a[1][1]) + fabs(a[2][2])))) break;
-    sym_rotate<0, 1, 2>(a, V);
-    sym_rotate<0, 2, 1>(a, V);
-    sym_rotate<1, 2, 0>(a, V);
-  }
-}
-
 __global__ __launch_bounds__(kNormalsThreads) void normals_kernel(RIndex ix, const double* __restrict__ xyz, int64_t M,
                                                                   double r, double radius,
                                                                   const double* __restrict__ viewpoints,
@@ -70,25 +33,13 @@ __global__ __launch_bounds__(kNormalsThreads) void normals_kernel(RIndex ix, con
   const int64_t i = ix.sidx[s];
   const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
   const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  int n = 0;
-  double m[3] = {0.0, 0.0, 0.0}, S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // sum e; sum e e^T: xx xy xz yy yz zz
-  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t, double ex, double ey, double ez) {
-    ++n;
-    m[0] += ex; m[1] += ey; m[2] += ez;
-    S[0] += ex * ex; S[1] += ex * ey; S[2] += ex * ez;
-    S[3] += ey * ey; S[4] += ey * ez; S[5] += ez * ez;
-  });
+  int n;
+  double m[3], S[6];   // sum e; sum e e^T: xx xy xz yy yz zz
+  ball_sums(ix, xyz, b, p, r, radius, n, m, S);
   double nv[3] = {0.0, 0.0, 1.0};
   if (n >= 3) {
-    const double inv = 1.0 / (double)n;
-    for (int e = 0; e < 3; ++e) m[e] *= inv;
     double a[3][3], V[3][3];
-    a[0][0] = S[0] * inv - m[0] * m[0];
-    a[0][1] = a[1][0] = S[1] * inv - m[0] * m[1];
-    a[0][2] = a[2][0] = S[2] * inv - m[0] * m[2];
-    a[1][1] = S[3] * inv - m[1] * m[1];
-    a[1][2] = a[2][1] = S[4] * inv - m[1] * m[2];
-    a[2][2] = S[5] * inv - m[2] * m[2];
+    ball_covariance(n, m, S, a);
     jacobi_eig3(a, V);
     // the column of the smallest eigenvalue; on equal values the last axis, as (0, 0, 1) is the default
     double v[3] = {V[0][2], V[1][2], V[2][2]}, lam = a[2][2];

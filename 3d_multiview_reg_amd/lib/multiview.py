@@ -501,11 +501,39 @@ def _denoise_arguments(denoise, r=None):
     return d
 
 
+def _keypoints_arguments(keypoints, r=None, init=None):
+    """register_scene's checks of `keypoints` that need no device (r: the index's cell size, where it is known) ->
+    None, or a dict of "match" and iss_keypoints' options with the defaults filled in (a radius left None stays
+    None)"""
+    from lib.fpfh import KEYPOINT_MATCH
+    from lib.overlap import ISS_DEFAULTS, _iss_arguments
+    if keypoints is None:
+        return None
+    if keypoints is not True and not isinstance(keypoints, dict):
+        raise ValueError("register_scene: keypoints must be None, True or a dict of iss_keypoints' options and 'match'")
+    if init is not None:
+        raise ValueError("register_scene: keypoints belong to the coarse registration, which init replaces")
+    given = {} if keypoints is True else keypoints
+    unknown = sorted(set(given) - set(ISS_DEFAULTS) - {"match"})
+    if unknown:
+        raise ValueError("register_scene: keypoints has no option %s" % ", ".join(map(repr, unknown)))
+    d = dict(dict(ISS_DEFAULTS, match="keypoints"), **given)
+    if d["match"] not in KEYPOINT_MATCH:
+        raise ValueError("register_scene: keypoints 'match' must be one of %s, not %r"
+                         % (", ".join(KEYPOINT_MATCH), d["match"]))
+    rr = float("inf") if r is None else float(r)
+    checked = _iss_arguments(*[d[k] for k in ISS_DEFAULTS], rr)
+    for k, v in zip(ISS_DEFAULTS, checked):
+        if d[k] is not None:
+            d[k] = v
+    return d
+
+
 def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=None, viewpoints=None, downsample=True,
                    dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
                    min_frags=1, min_points=1, ransac_checkers=False, line_process=False,
-                   preference_loop_closure=1.0, denoise=None, coarse="ransac"):
+                   preference_loop_closure=1.0, denoise=None, coarse="ransac", keypoints=None):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
@@ -519,7 +547,10 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
       3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed` and
          checkers=ransac_checkers (True or a dict: RANSAC with correspondence checkers and 100000 draws), or with
          coarse="fgr" lib.fpfh.register_fgr (Fast Global Registration, `seed` keying its tuple filter; not with
-         ransac_checkers.  It wants matches with tens of percent inliers: RANSAC stays the default)
+         ransac_checkers.  It wants matches with tens of percent inliers: RANSAC stays the default);
+         keypoints (None: every point is matched, as without it): True, or a dict of fo.iss_keypoints' options and
+         "match" ('keypoints' or 'all', lib.fpfh.match_keypoints) — ISS keypoints are detected once and the matching
+         of either estimator runs on them (not with init)
          (init [P,4,4], x_j ~ T x_i for the pairs i < j in that order, replaces 3 and 4);
       5. the overlap gate of the pairwise benchmark: a pair is kept when FragmentOverlap.ratios >= overlap_threshold
          (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
@@ -534,7 +565,8 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     refinement, 0 where not kept; with line_process also pruned bool [P]: the pose graph dropped the pair), sync and
     refined (the dicts of synchronize and optimize_pose_graph), fo, and scene (the dict of fuse_scene); with denoise
     also denoise: keep (numpy bool over the points of step 1, fo.parent_rows are the kept ones) and removed [n] (the
-    points each fragment lost)."""
+    points each fragment lost); with keypoints also keypoints: rows [K] (rows of fo.xyz, ascending) and off [n+1]
+    (numpy int64)."""
     from lib.fpfh import register_fgr, register_fpfh
     from lib.icp import gicp_refine, icp_refine, information_matrix
     from lib.overlap import FragmentOverlap
@@ -545,6 +577,7 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
         raise ValueError("register_scene: ransac_checkers belongs to coarse='ransac', not to coarse='fgr'")
     pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints)
     denoise = _denoise_arguments(denoise, 3.0 * float(voxel_size))
+    keypoints = _keypoints_arguments(keypoints, 3.0 * float(voxel_size), init)
     threshold = OVERLAP_THRESHOLDS[dataset] if overlap_threshold is None else float(overlap_threshold)
     P = len(pairs)
     if downsample:
@@ -563,10 +596,14 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     fo.estimate_normals(normal_radius, viewpoints)
     if init is None:
         fo.compute_fpfh(fpfh_radius)
+        kp_args = {}
+        if keypoints is not None:
+            detected = fo.iss_keypoints(**{k: v for k, v in keypoints.items() if k != "match"})
+            kp_args = {"keypoints": detected, "match": keypoints["match"]}
         if coarse == "fgr":
-            T_coarse = np.asarray(register_fgr(fo, pairs, seed=seed)["T"], dtype=np.float64)
+            T_coarse = np.asarray(register_fgr(fo, pairs, seed=seed, **kp_args)["T"], dtype=np.float64)
         else:
-            T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed, checkers=ransac_checkers)["T"],
+            T_coarse = np.asarray(register_fpfh(fo, pairs, seed=seed, checkers=ransac_checkers, **kp_args)["T"],
                                   dtype=np.float64)
     else:
         T_coarse = init
@@ -606,4 +643,6 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
               "fo": fo, "scene": scene}
     if denoised is not None:
         result["denoise"] = denoised
+    if keypoints is not None:
+        result["keypoints"] = {"rows": detected["rows"].cpu().numpy(), "off": detected["off"]}
     return result

@@ -58,6 +58,36 @@ def _radius_outlier_arguments(nb_points, radius, r):
     return int(nb_points), radius
 
 
+ISS_DEFAULTS = {"salient_radius": None, "non_max_radius": None, "gamma_21": 0.975, "gamma_32": 0.975,
+                "min_neighbors": 5, "min_ratio": 1e-6}
+
+
+def _iss_arguments(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, min_ratio, r):
+    """iss_keypoints' checks that need no device, r the index's cell size -> (salient_radius, non_max_radius,
+    gamma_21, gamma_32, min_neighbors, min_ratio) with the defaults filled in (salient r, non-max 2/3 r: Open3D's
+    6 : 4 ratio)"""
+    r = float(r)
+    radii = []
+    for name, v, default in (("salient_radius", salient_radius, r), ("non_max_radius", non_max_radius, 2.0 * r / 3.0)):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 < float(v) <= r:
+            raise ValueError("iss_keypoints: %s %r must lie in (0, %g], the index's cell size (build the "
+                             "FragmentOverlap with radius >= it)" % (name, v, r))
+        radii.append(float(v))
+    gammas = []
+    for name, v in (("gamma_21", gamma_21), ("gamma_32", gamma_32)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 < float(v) <= 1.0:
+            raise ValueError("iss_keypoints: %s must lie in (0, 1], not %r" % (name, v))
+        gammas.append(float(v))
+    if isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer)) or int(min_neighbors) < 1 \
+            or int(min_neighbors) > 0x7fffffff:
+        raise ValueError("iss_keypoints: min_neighbors must be a positive integer, not %r" % (min_neighbors,))
+    if isinstance(min_ratio, bool) or not isinstance(min_ratio, (int, float, np.floating, np.integer)) \
+            or not 0.0 <= float(min_ratio) < 1.0:
+        raise ValueError("iss_keypoints: min_ratio must lie in [0, 1), not %r" % (min_ratio,))
+    return radii[0], radii[1], gammas[0], gammas[1], int(min_neighbors), float(min_ratio)
+
+
 def _keep_mask(keep, M):
     """select's check of its mask -> a bool tensor [M] (on whatever device keep was)"""
     keep = torch.as_tensor(np.asarray(keep) if not torch.is_tensor(keep) else keep)
@@ -207,6 +237,36 @@ class FragmentOverlap(object):
                                          self.B, self.M, self.r, radius, N.ptr(count), N.stream()),
                 "mvr_radius_count")
         return {"keep": count > nb_points, "count": count}
+
+    def iss_keypoints(self, salient_radius=None, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5,
+                      min_ratio=1e-6):
+        """Open3D's compute_iss_keypoints per fragment, restated (csrc/iss.hip mvr_iss_saliency + mvr_radius_nms;
+        the semantics are in include/mvreg.h).  With l1 >= l2 >= l3 the eigenvalues of the covariance of the points
+        closer than salient_radius (None: fo.r), a point is a candidate with saliency l3 when it has at least
+        min_neighbors of them, l2 < gamma_21 l1, l3 < gamma_32 l2 and l3 > min_ratio l1 (0: Open3D's rule; the default
+        keeps rounding noise on planes from deciding); a candidate is a keypoint when no point closer than
+        non_max_radius (None: 2/3 fo.r) has a larger saliency (ties: the lower row; Open3D keeps both) and that ball
+        holds at least min_neighbors points.  Both radii at most fo.r.
+        -> {"keep": bool [M], "saliency": fp64 [M] (-1 where not a candidate), "n_nbr": int32 [M], "rows": int64 [K]
+        the kept rows of fo.xyz ascending (all on the device), "off": numpy int64 [B+1] the prefix sums of the
+        keypoints per fragment}; fo.select(keep) applies it."""
+        sal_r, nms_r, g21, g32, min_n, min_ratio = _iss_arguments(salient_radius, non_max_radius, gamma_21, gamma_32,
+                                                                  min_neighbors, min_ratio, self.r)
+        L = N.lib()
+        saliency = torch.empty(self.M, dtype=torch.float64, device=self.device)
+        n_nbr = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        keep = torch.empty(self.M, dtype=torch.uint8, device=self.device)
+        N.check(L.mvr_iss_saliency(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev), self.B,
+                                   self.M, self.r, sal_r, g21, g32, min_ratio, min_n, N.ptr(saliency), N.ptr(n_nbr),
+                                   N.stream()), "mvr_iss_saliency")
+        N.check(L.mvr_radius_nms(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev), self.B,
+                                 self.M, self.r, nms_r, min_n, N.ptr(saliency), N.ptr(keep), N.stream()),
+                "mvr_radius_nms")
+        keep = keep.bool()
+        rows = torch.nonzero(keep).reshape(-1)
+        kept_before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), keep.long().cumsum(0)])
+        off = kept_before.cpu().numpy()[self.off].astype(np.int64)
+        return {"keep": keep, "saliency": saliency, "n_nbr": n_nbr, "rows": rows, "off": off}
 
     def select(self, keep):
         """A new FragmentOverlap over the rows with keep[i] (bool / uint8 [M], array or tensor), in their order: the

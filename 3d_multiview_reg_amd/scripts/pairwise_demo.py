@@ -13,8 +13,9 @@ usage: python -m scripts.pairwise_demo configs/pairwise_registration/demo/config
 --fpfh registers the pair without any network or checkpoint (lib/fpfh.py): voxel centroids at the
 config's voxel_size, normals oriented to each cloud's mean, FPFH descriptors, mutual feature matches, RANSAC and,
 with --icp, a point-to-point ICP refinement; T is printed and written to the same est_T.log.  --fpfh --fgr runs Fast
-Global Registration (lib.fpfh.register_fgr) on the matches in place of RANSAC.
-    [--fpfh [--fpfh_radius R] [--normal_radius R] [--checkers | --fgr] [--icp]]   (defaults: 5 and 2 voxel sizes)
+Global Registration (lib.fpfh.register_fgr) on the matches in place of RANSAC.  --fpfh --iss matches
+the descriptors of ISS keypoints only (FragmentOverlap.iss_keypoints).
+    [--fpfh [--fpfh_radius R] [--normal_radius R] [--checkers | --fgr] [--iss] [--icp]]   (defaults: 5 and 2 voxel sizes)
 """
 import argparse
 import logging
@@ -72,10 +73,16 @@ def main_fpfh(cfg, args, logger=logging.getLogger()):
     fo.estimate_normals(r_normal, viewpoints=[xyz[fo.off[b]:fo.off[b + 1]].mean(0) for b in range(2)])
     fo.compute_fpfh(r_fpfh)
     fgr = bool(getattr(args, "fgr", False))
+    kp = {}
+    if getattr(args, "iss", False):   # register_scene's radii: 3 and 2 voxel sizes, where the index allows them
+        kp = {"keypoints": fo.iss_keypoints(min(fo.r, 3.0 * voxel), min(fo.r, 2.0 * voxel))}
     if fgr:
-        out = register_fgr(fo, [[0, 1]])
+        out = register_fgr(fo, [[0, 1]], **kp)
     else:
-        out = register_fpfh(fo, [[0, 1]], checkers=bool(getattr(args, "checkers", False)))
+        out = register_fpfh(fo, [[0, 1]], checkers=bool(getattr(args, "checkers", False)), **kp)
+    if kp:
+        print("ISS: %d / %d keypoints of %d / %d points" % (out["n_keypoints"][0, 0], out["n_keypoints"][0, 1],
+                                                            fo.off[1], fo.off[2] - fo.off[1]))
     if "n_pass" in out:
         logger.info("checkers: %d of 100000 samples passed, %d scored", out["n_pass"][0], out["n_valid"][0])
     est_T = out["T"][0]
@@ -97,7 +104,9 @@ def main_fpfh(cfg, args, logger=logging.getLogger()):
 
 
 def check_args(args):
-    """ValueError for --fgr without --fpfh or with --checkers"""
+    """ValueError for --fgr or --iss without --fpfh, and for --fgr with --checkers"""
+    if getattr(args, "iss", False) and not getattr(args, "fpfh", False):
+        raise ValueError("--iss picks the points whose FPFH descriptors are matched: it needs --fpfh")
     if getattr(args, "fgr", False):
         if not getattr(args, "fpfh", False):
             raise ValueError("--fgr registers the FPFH matches: it needs --fpfh")
@@ -163,6 +172,8 @@ def parser():
                     help="With --fpfh: RANSAC with edge-length and distance checkers, 3-point samples, 100000 draws.")
     ap.add_argument("--fgr", action="store_true",
                     help="With --fpfh: Fast Global Registration on the matches instead of RANSAC (not with --checkers).")
+    ap.add_argument("--iss", action="store_true",
+                    help="With --fpfh: match the descriptors of ISS keypoints only (Open3D's compute_iss_keypoints).")
     ap.add_argument("--icp", action="store_true", help="With --fpfh: refine the estimate by point-to-point ICP.")
     return ap
 

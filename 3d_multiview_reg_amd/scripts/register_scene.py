@@ -12,10 +12,13 @@ refinement and the fused cloud, all on the GPU.  Writes into --out
 gate is an uncertain edge); the pairs it pruned are counted in the printed line.
 --denoise statistical:20:2.0 | radius:16[:R]: Open3D's statistical / radius outlier removal on each fragment's centroids
 before anything else uses them; the points removed per fragment are printed.
+--keypoints iss[:SALIENT:NONMAX]: ISS keypoints (Open3D's compute_iss_keypoints; radii default to 3 and 2 voxel sizes)
+are detected on each fragment and the FPFH matching runs on them alone; the keypoints per fragment are printed.
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
            [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
            [--checkers | --coarse fgr] [--line_process [--preference_loop_closure 1.0]] [--denoise statistical:20:2.0]
+           [--keypoints iss[:SALIENT:NONMAX]]
 """
 import argparse
 import os
@@ -64,6 +67,21 @@ def parse_denoise(text):
     return d
 
 
+def parse_keypoints(text):
+    """'iss' or 'iss:SALIENT:NONMAX' -> register_scene's keypoints dict (ValueError on anything else)"""
+    parts = text.split(":")
+    try:
+        if parts[0] == "iss" and len(parts) == 1:
+            d = {}
+        elif parts[0] == "iss" and len(parts) == 3:
+            d = {"salient_radius": float(parts[1]), "non_max_radius": float(parts[2])}
+        else:
+            raise ValueError("neither form")
+    except ValueError:
+        raise ValueError("--keypoints must be iss or iss:SALIENT_RADIUS:NON_MAX_RADIUS, not %r" % (text,))
+    return d
+
+
 def parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--fragments", required=True, nargs="+", help="the fragments' PLY files (at least two)")
@@ -88,6 +106,10 @@ def parser():
                     help="remove outliers from the centroids before registration: statistical:20:2.0 (Open3D's "
                          "remove_statistical_outlier(nb_neighbors, std_ratio)) or radius:16[:R] "
                          "(remove_radius_outlier(nb_points, radius), R at most 3 voxel_size, its default)")
+    ap.add_argument("--keypoints", default=None, metavar="SPEC",
+                    help="match the FPFH descriptors of ISS keypoints only: iss, or iss:SALIENT:NONMAX (Open3D's "
+                         "compute_iss_keypoints radii, each at most 3 voxel_size; defaults 3 and 2 voxel_size); not "
+                         "with --init")
     return ap
 
 
@@ -110,6 +132,12 @@ def check_args(ap, a):
             a.denoise = _denoise_arguments(parse_denoise(a.denoise), 3.0 * a.voxel_size)
         except ValueError as e:
             ap.error(str(e))
+    if a.keypoints is not None:
+        from lib.multiview import _keypoints_arguments
+        try:
+            a.keypoints = _keypoints_arguments(parse_keypoints(a.keypoints), 3.0 * a.voxel_size, a.init)
+        except ValueError as e:
+            ap.error(str(e))
     return a
 
 
@@ -124,7 +152,8 @@ def main(argv=None):
                          **({} if a.coarse == "ransac" else dict(coarse=a.coarse)),
                          **({} if not a.line_process else dict(line_process=True,
                                                                preference_loop_closure=a.preference_loop_closure)),
-                         **({} if a.denoise is None else dict(denoise=a.denoise)))
+                         **({} if a.denoise is None else dict(denoise=a.denoise)),
+                         **({} if a.keypoints is None else dict(keypoints=a.keypoints)))
     ensure_dir(a.out)
     write_poses(res["poses"], os.path.join(a.out, "poses.txt"))
     rec = res["pairs"]
@@ -141,6 +170,8 @@ def main(argv=None):
     if a.denoise is not None:
         print("denoise (%s): points removed per fragment: %s"
               % (a.denoise["method"], " ".join(str(int(v)) for v in res["denoise"]["removed"])))
+    if a.keypoints is not None:
+        print("keypoints (iss): per fragment: %s" % " ".join(str(int(v)) for v in np.diff(res["keypoints"]["off"])))
     if a.line_process:
         print("line process: %d of the %d gated pairs pruned" % (int(rec["pruned"].sum()), int(rec["kept"].sum())))
     return res

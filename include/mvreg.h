@@ -388,7 +388,8 @@ int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
  * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane,
- * mvr_icp_refine_generalized, mvr_compute_fpfh, mvr_knn_self and mvr_radius_count calls on the same points.
+ * mvr_icp_refine_generalized, mvr_compute_fpfh, mvr_knn_self, mvr_radius_count, mvr_iss_saliency and mvr_radius_nms
+ * calls on the same points.
  * B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
@@ -636,6 +637,40 @@ int mvr_statistical_outlier(const double* dist2, const int64_t* off, int B, int6
                             uint8_t* keep, double* mean_dist, double* thr, mvr_stream_t stream);
 int mvr_radius_count(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
                      double r_index, double radius, int32_t* count, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * ISS keypoints (Intrinsic Shape Signatures, Zhong 2009) of every fragment's own points, on a radius index
+ * (csrc/iss.hip): Open3D's compute_iss_keypoints restated from the maths, each fragment its own cloud;
+ * Open3D parity is unpinned.  tests/iss_oracle.py is the numpy restatement.  Two launches, each one thread per point,
+ * fp64, no atomics, no workspace; a point's outputs are a function of its fragment alone and repeat bit for bit.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`.
+ * mvr_iss_saliency: the neighbours of point i are the points of its fragment with
+ *   sqrt(ex*ex + ey*ey + ez*ez) < salient_radius, e = x_j - x_i (strict, i itself among them: the set and the count
+ *   n_nbr of mvr_estimate_normals).  C = their covariance about their own mean, divided by n, accumulated in
+ *   coordinates relative to x_i; l1 >= l2 >= l3 its eigenvalues (cyclic Jacobi).  saliency[i] = l3 when
+ *   n >= min_neighbors, l3 > min_ratio l1, l2 < gamma_21 l1 and l3 < gamma_32 l2; exactly -1.0 otherwise.  The
+ *   products are Open3D's quotients l2 / l1 < gamma_21, l3 / l2 < gamma_32 without the divisions.  min_ratio is an
+ *   addition: on a planar neighbourhood l3 is zero up to rounding, which would otherwise decide; 0 gives
+ *   Open3D's rule.  n_nbr [M] may be NULL.  Every saliency[i] and n_nbr[i] is written.
+ *   MVR_EINVAL, scalars first: negative M or M >= 2^31; B <= 0 or B >= 32768; r_index <= 0; salient_radius outside
+ *   (0, r_index]; a gamma outside (0, 1]; min_ratio outside [0, 1); min_neighbors < 1 (NaN is outside every range).
+ *   M == 0 then returns MVR_OK.  With M > 0: a NULL index, xyz, off or saliency, or
+ *   index_bytes < mvr_radius_index_bytes(M).
+ * mvr_radius_nms: non-maximum suppression of any score [M] over the ball of `radius` (the same membership rule).
+ *   keep[i] = 1 when score[i] > 0, the ball of i holds at least min_neighbors points (i among them), and no point
+ *   j != i of the ball has score[j] > score[i], or score[j] == score[i] with j < i; 0 otherwise.  Every keep[i] is
+ *   written.  A NaN score is never kept and never suppresses (every comparison with it is false).
+ *   The tie rule differs from Open3D on purpose: Open3D keeps both points of a tie, so duplicated points (which share
+ *   their neighbours and hence their saliency) give duplicated keypoints; here only the lower row survives.
+ *   MVR_EINVAL, scalars first: as above with `radius`; M == 0 then returns MVR_OK.  With M > 0: a NULL index, xyz,
+ *   off, score or keep, or index_bytes < mvr_radius_index_bytes(M).
+ * ---------------------------------------------------------------------- */
+int mvr_iss_saliency(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
+                     double r_index, double salient_radius, double gamma_21, double gamma_32, double min_ratio,
+                     int min_neighbors, double* saliency, int32_t* n_nbr, mvr_stream_t stream);
+int mvr_radius_nms(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
+                   double r_index, double radius, int min_neighbors, const double* score, uint8_t* keep,
+                   mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Nearest neighbour in feature space between ragged fragments (csrc/feat_match.hip), for any channel
