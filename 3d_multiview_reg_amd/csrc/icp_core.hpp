@@ -1,11 +1,15 @@
 // What the radius-index nearest-neighbour kernels share: the search of the nearest target point
-// (icp.hip, icp_plane.hip, icp_gicp.hip, info.hip), the validation of a pair, and for the three ICP kernels the args
-// struct with its host-side checks, the loop with its stopping rule, trace and status bits, and the 6 x 6 solve with
-// the update of T.  A kernel supplies a model: what a match adds to the sums and what lane 0 solves from them.
-// Everything is inlined into the kernel that uses it; each of the four sources stays its own translation unit.
+// (icp.hip, icp_plane.hip, icp_gicp.hip, icp_robust.hip, info.hip), the validation of a pair, and for the ICP kernels
+// the args struct with its host-side checks, the loop with its stopping rule, trace and status bits, and the 6 x 6
+// solve with the update of T.  A kernel supplies a model: what a match adds to the sums and what lane 0 solves from
+// them.
+// The three models live here too, each with a weight policy: UnitWeight for the plain kernels, where
+// the weight is a type and nothing is generated for it, KernelWeight for icp_robust.hip's robust kernels.
+// Everything is inlined into the kernel that uses it; each of the five sources stays its own translation unit.
 #pragma once
 #include "common.hpp"
 #include "rindex.hpp"
+#include "svd3.hpp"
 #include "mvreg.h"
 #include <math.h>
 
@@ -131,16 +135,52 @@ struct IcpArgs {
   double* T; double* fitness; double* rmse; int32_t* n_corr; int32_t* iters; int32_t* status; double* trace;
 };
 
+// mvr_icp_refine_robust's: the kernel and its scale (uniform), and where sum w of the returned T's evaluation goes
+struct RobustArgs : IcpArgs {
+  int kernel; double kernel_k; double* w_sum;
+};
+
+// ----------------------------------------------------------------------------------------------------- weight policies
+// What a model multiplies a match's terms with.  The plain kernels' weight is a type: w * x is x, and neither the
+// residual nor a product is generated for it, so their code is what it was without weights.
+struct Unit {};
+__device__ __forceinline__ double operator*(Unit, double x) { return x; }
+struct UnitWeight {
+  using Args = IcpArgs;
+  static constexpr bool kWeighted = false;
+  template <class Residual>
+  __device__ __forceinline__ static Unit weight(const Args&, Residual&&) { return {}; }
+};
+// w(r) of mvreg.h mvr_icp_refine_robust, k > 0: one switch on a uniform value per match, after the search.  Every
+// weight is continuous in r, Tukey's at |r| == k too (u == 0 there).  L2 is exactly 1.0, and x * 1.0 is x exactly
+struct KernelWeight {
+  using Args = RobustArgs;
+  static constexpr bool kWeighted = true;
+  template <class Residual>
+  __device__ __forceinline__ static double weight(const Args& a, Residual&& residual) {
+    if (a.kernel == MVR_KERNEL_L2) return 1.0;
+    const double k = a.kernel_k, r = residual();
+    switch (a.kernel) {
+      case MVR_KERNEL_HUBER: return k / fmax(fabs(r), k);
+      case MVR_KERNEL_CAUCHY: { const double s = r / k; return 1.0 / (1.0 + s * s); }
+      case MVR_KERNEL_GM: { const double s = k + r * r; return k / (s * s); }
+      default: { const double s = r / k, u = 1.0 - s * s; return fabs(r) <= k ? u * u : 0.0; }   // Tukey
+    }
+  }
+};
+
 // The loop of one pair, every iteration inside the one launch (mvreg.h mvr_icp_refine has the semantics).  Model:
 //   kSums, kMinCorr, kOrigin   the number of sums (the first two are n and sum d^2, added here), the least number of
 //                              correspondences for a solve, the doubles of the origin
+//   Args, kWeighted            IcpArgs / false, or RobustArgs / true: then the last sum is sum w, and it goes to w_sum
 //   kCanFail                   whether solve can return false; where it cannot, nothing refers to the verdict's LDS
 //                              word and the compiler drops it (LDS 2320 B for point-to-point)
 //   origin(a, g, T0, sO)       lane 0: the per-pair origin of the sums
-//   accumulate(a, sT, sO, v, i, bt, q)   what source row i, moved to q and matched with target row bt, adds to v[2:]
+//   accumulate(a, sT, sO, v, i, bt, q, d2)   what source row i, moved to q and matched with target row bt at squared
+//                              distance d2, adds to v[2:]
 //   solve(v, sT, sO) -> bool   lane 0: the next T into sT from the block's sums; false ends the loop with status bit 8
 template <class Model, int kThreads>
-__device__ __forceinline__ void icp_loop(const IcpArgs& a) {
+__device__ __forceinline__ void icp_loop(const typename Model::Args& a) {
   constexpr int kSums = Model::kSums;
   __shared__ double red[kSums * (kThreads / 64)];
   __shared__ double sT[12], sO[Model::kOrigin];   // the current T; the origin of the sums
@@ -160,6 +200,8 @@ __device__ __forceinline__ void icp_loop(const IcpArgs& a) {
       if (a.n_corr) a.n_corr[p] = 0;
       if (a.iters) a.iters[p] = 0;
       a.status[p] = 4;
+      if constexpr (Model::kWeighted)
+        if (a.w_sum) a.w_sum[p] = 0.0;
     }
     if (trace)
       for (int64_t e = tid; e < 2 * rows; e += kThreads) trace[e] = -1.0;
@@ -187,7 +229,7 @@ __device__ __forceinline__ void icp_loop(const IcpArgs& a) {
       moved_point(sT, a.xyz, i, q);
       const int64_t bt = nearest_row(a.ix, a.xyz, g.tf, q, r, slack, md2, a.max_dist, best);
       if (bt >= 0) {
-        Model::accumulate(a, sT, sO, v, i, bt, q);
+        Model::accumulate(a, sT, sO, v, i, bt, q, best);
         v[0] += 1.0;
         v[1] += best;
       }
@@ -218,15 +260,82 @@ __device__ __forceinline__ void icp_loop(const IcpArgs& a) {
     if (a.n_corr) a.n_corr[p] = n;
     if (a.iters) a.iters[p] = k;
     a.status[p] = status;
+    if constexpr (Model::kWeighted)
+      if (a.w_sum) a.w_sum[p] = v[kSums - 1];   // of the last evaluation: the returned T's, also after a failed solve
   }
   if (trace)
     for (int64_t e = 2 * ((int64_t)k + 1) + tid; e < 2 * rows; e += kThreads) trace[e] = -1.0;
 }
 
+// ------------------------------------------------------------------------------------------------------------ models
+// Point-to-point (mvreg.h mvr_icp_refine): count, sum d^2, sum w x, sum w y, sum w x y^T per thread in registers,
+// relative to a per-pair origin (the source fragment's first point and its image under T0), so that
+// sum w x y^T - W mx my^T cancels little; weighted also W = sum w.  Lane 0 solves: centred covariance from the sums,
+// jacobi_svd3, det-corrected R, t
+template <class Wt>
+struct PointToPointT {
+  using Args = typename Wt::Args;
+  static constexpr bool kWeighted = Wt::kWeighted;
+  static constexpr int kSums = 17 + kWeighted;   // n, sum d^2, sum x [3], sum y [3], sum x y^T [9], (sum w)
+  static constexpr int kMinCorr = 3, kOrigin = 6;   // the origins of the sums: source side, target side
+  static constexpr bool kCanFail = kWeighted;       // sum w > 0 can fail; a count >= 3 cannot
+
+  __device__ __forceinline__ static void origin(const IcpArgs& a, const PairRange& g, const double* T0, double* sO) {
+    double o[3] = {0.0, 0.0, 0.0};
+    if (g.s0 < g.s1)
+      for (int e = 0; e < 3; ++e) o[e] = a.xyz[3 * g.s0 + e];
+    for (int e = 0; e < 3; ++e) {
+      sO[e] = o[e];
+      sO[3 + e] = T0[4 * e] * o[0] + T0[4 * e + 1] * o[1] + T0[4 * e + 2] * o[2] + T0[4 * e + 3];
+    }
+  }
+
+  __device__ __forceinline__ static void accumulate(const Args& a, const double* sT, const double* sO,
+                                                    double (&v)[kSums], int64_t i, int64_t bt, const double (&q)[3],
+                                                    double d2) {
+    // x is read again (moved_point had it): the same values, and no register held across the search for it
+    const double xr[3] = {a.xyz[3 * i] - sO[0], a.xyz[3 * i + 1] - sO[1], a.xyz[3 * i + 2] - sO[2]};
+    const double yr[3] = {a.xyz[3 * bt] - sO[3], a.xyz[3 * bt + 1] - sO[4], a.xyz[3 * bt + 2] - sO[5]};
+    const auto w = Wt::weight(a, [&] { return sqrt(d2); });   // r = |q - y|, the search's own distance
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      const double wx = w * xr[e];
+      v[2 + e] += wx;
+      v[5 + e] += w * yr[e];
+#pragma unroll
+      for (int f = 0; f < 3; ++f) v[8 + 3 * e + f] += wx * yr[f];
+    }
+    if constexpr (kWeighted) v[kSums - 1] += w;
+  }
+
+  // argmin sum w |R x + t - y|^2 over the valid pairs, on the original source points.  false: not sum w > 0
+  __device__ __forceinline__ static bool solve(const double (&v)[kSums], double* sT, const double* sO) {
+    const double W = kWeighted ? v[kSums - 1] : v[0];
+    if constexpr (kWeighted)
+      if (!(W > 0.0)) return false;
+    double mx[3], my[3], H[3][3], U[3][3], S[3], V[3][3];
+    for (int e = 0; e < 3; ++e) { mx[e] = v[2 + e] / W; my[e] = v[5 + e] / W; }
+    for (int e = 0; e < 3; ++e)
+      for (int f = 0; f < 3; ++f) H[e][f] = v[8 + 3 * e + f] - W * mx[e] * my[f];
+    jacobi_svd3(H, U, S, V);
+    const double d = det3(U) * det3(V) < 0.0 ? -1.0 : 1.0;
+    for (int e = 0; e < 3; ++e) {
+      double R[3];
+      for (int f = 0; f < 3; ++f) R[f] = V[e][0] * U[f][0] + V[e][1] * U[f][1] + d * V[e][2] * U[f][2];
+      for (int f = 0; f < 3; ++f) sT[4 * e + f] = R[f];
+      sT[4 * e + 3] = (my[e] + sO[3 + e]) - (R[0] * (mx[0] + sO[0]) + R[1] * (mx[1] + sO[1]) + R[2] * (mx[2] + sO[2]));
+    }
+    return true;
+  }
+};
+
 // What the models of point-to-plane and generalized ICP share: the layout of the sums, the origin c (the target
 // fragment's first point, so that the cross products stay small) and the solve.  Theirs is accumulate
-struct SixDofModel {
-  static constexpr int kSums = 29;   // n, sum d^2, upper triangle of H [21], g [6]
+template <class Wt>
+struct SixDofModelT {
+  using Args = typename Wt::Args;
+  static constexpr bool kWeighted = Wt::kWeighted;
+  static constexpr int kSums = 29 + kWeighted;   // n, sum d^2, upper triangle of H [21], g [6], (sum w)
   static constexpr int kMinCorr = 6, kOrigin = 3;
   static constexpr bool kCanFail = true;
 
@@ -235,7 +344,7 @@ struct SixDofModel {
   }
 
   // xi = -H^-1 g, then T <- D T in sT with D = [R_inc | xi[3:6] + c - R_inc c], R_inc = Rz(xi2) Ry(xi1) Rx(xi0).
-  // false: H is not positive definite to working precision, sT kept
+  // false: H is not positive definite to working precision (all weights zero: the first pivot), sT kept
   __device__ __forceinline__ static bool solve(const double (&v)[kSums], double* sT, const double* sC) {
     double xi[6];
     if (!solve6(v + 2, v + 23, xi)) return false;
@@ -250,6 +359,100 @@ struct SixDofModel {
     }
     for (int q = 0; q < 12; ++q) sT[q] = Tn[q];
     return true;
+  }
+};
+using SixDofModel = SixDofModelT<UnitWeight>;   // fgr.hip solves its own 6 x 6 system with it
+
+// Point-to-plane (mvreg.h mvr_icp_refine_plane).  Per match, in registers: of a = [(q - c) x n, n], b = (q - y) . n
+// (n the normal of the match y) the upper triangle of sum w a a^T (21) and sum w a b (6); the weight's residual is b
+template <class Wt>
+struct PointToPlaneT : SixDofModelT<Wt> {
+  using Base = SixDofModelT<Wt>;
+  using Base::kSums;
+  __device__ __forceinline__ static void accumulate(const typename Base::Args& a, const double* sT, const double* sC,
+                                                    double (&v)[kSums], int64_t i, int64_t bt, const double (&q)[3],
+                                                    double d2) {
+    const double n[3] = {a.normals[3 * bt], a.normals[3 * bt + 1], a.normals[3 * bt + 2]};
+    const double e[3] = {q[0] - a.xyz[3 * bt], q[1] - a.xyz[3 * bt + 1], q[2] - a.xyz[3 * bt + 2]};
+    const double w[3] = {q[0] - sC[0], q[1] - sC[1], q[2] - sC[2]};
+    const double ja[6] = {w[1] * n[2] - w[2] * n[1], w[2] * n[0] - w[0] * n[2], w[0] * n[1] - w[1] * n[0],
+                          n[0], n[1], n[2]};
+    const double b = e[0] * n[0] + e[1] * n[1] + e[2] * n[2];
+    const auto wt = Wt::weight(a, [&] { return b; });
+    int h = 2;   // (w a_f) a_g: with w == 1.0 the products and their FMAs are those of the unweighted sums
+#pragma unroll
+    for (int f = 0; f < 6; ++f)
+#pragma unroll
+      for (int g = f; g < 6; ++g) v[h++] += (wt * ja[f]) * ja[g];
+#pragma unroll
+    for (int f = 0; f < 6; ++f) v[23 + f] += (wt * ja[f]) * b;
+    if constexpr (Base::kWeighted) v[kSums - 1] += wt;
+  }
+};
+
+// Generalized (mvreg.h mvr_icp_refine_generalized; icp_gicp.hip has the algebra).  Per match, in registers: the two
+// normals are loaded, n_s rotated, M inverted and the products formed only once a match is found, so nothing of it is
+// live across the search.  The residual of the weight is sqrt(d^T A d); the weight enters as w A
+template <class Wt>
+struct GeneralizedT : SixDofModelT<Wt> {
+  using Base = SixDofModelT<Wt>;
+  using Base::kSums;
+  __device__ __forceinline__ static void accumulate(const typename Base::Args& a, const double* sT, const double* sC,
+                                                    double (&v)[kSums], int64_t i, int64_t bt, const double (&q)[3],
+                                                    double d2) {
+    const double ome = 1.0 - a.epsilon;
+    const double n[3] = {a.normals[3 * bt], a.normals[3 * bt + 1], a.normals[3 * bt + 2]};
+    const double sx = a.normals[3 * i], sy = a.normals[3 * i + 1], sz = a.normals[3 * i + 2];
+    const double m[3] = {sT[0] * sx + sT[1] * sy + sT[2] * sz, sT[4] * sx + sT[5] * sy + sT[6] * sz,
+                         sT[8] * sx + sT[9] * sy + sT[10] * sz};
+    // M = 2 I - (1 - eps)(n n^T + m m^T) by its upper triangle (00 01 02 11 12 22), A = adj(M) / det(M)
+    const double m00 = 2.0 - ome * (n[0] * n[0] + m[0] * m[0]), m01 = -ome * (n[0] * n[1] + m[0] * m[1]),
+                 m02 = -ome * (n[0] * n[2] + m[0] * m[2]), m11 = 2.0 - ome * (n[1] * n[1] + m[1] * m[1]),
+                 m12 = -ome * (n[1] * n[2] + m[1] * m[2]), m22 = 2.0 - ome * (n[2] * n[2] + m[2] * m[2]);
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double inv = 1.0 / (m00 * c00 + m01 * c01 + m02 * c02);
+    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const double e[3] = {q[0] - a.xyz[3 * bt], q[1] - a.xyz[3 * bt + 1], q[2] - a.xyz[3 * bt + 2]};
+    const double w[3] = {q[0] - sC[0], q[1] - sC[1], q[2] - sC[2]};
+    // The weight scales 1 / det(M), and everything below is linear in A = adj(M) (w / det(M)): with a weight of exactly
+    // 1.0 every product and every FMA below is that of the unweighted sums.  A weight applied later would not do: the
+    // compiler fuses a term's last product with the addition to its sum (the entries adj * inv of A that enter H as
+    // they are, the cross products' second halves), so a product in between rounds once more
+    const auto wt = Wt::weight(a, [&] {
+      const double dCd = e[0] * (c00 * e[0] + c01 * e[1] + c02 * e[2]) + e[1] * (c01 * e[0] + c11 * e[1] + c12 * e[2]) +
+                         e[2] * (c02 * e[0] + c12 * e[1] + c22 * e[2]);
+      return sqrt(fmax(dCd * inv, 0.0));   // sqrt(d^T A d)
+    });
+    const double winv = wt * inv;
+    const double A[3][3] = {{c00 * winv, c01 * winv, c02 * winv},
+                            {c01 * winv, c11 * winv, c12 * winv},
+                            {c02 * winv, c12 * winv, c22 * winv}};
+    // Bm = S A: column j is w x A[:, j];  Cm = S A S^T: row f is w x Bm[f, :];  gd = [w x (A d), A d]
+    double Bm[3][3], Cm[3][3], gd[6];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      Bm[0][j] = w[1] * A[2][j] - w[2] * A[1][j];
+      Bm[1][j] = w[2] * A[0][j] - w[0] * A[2][j];
+      Bm[2][j] = w[0] * A[1][j] - w[1] * A[0][j];
+    }
+#pragma unroll
+    for (int f = 0; f < 3; ++f) {
+      Cm[f][0] = w[1] * Bm[f][2] - w[2] * Bm[f][1];
+      Cm[f][1] = w[2] * Bm[f][0] - w[0] * Bm[f][2];
+      Cm[f][2] = w[0] * Bm[f][1] - w[1] * Bm[f][0];
+      gd[3 + f] = A[f][0] * e[0] + A[f][1] * e[1] + A[f][2] * e[2];
+    }
+    gd[0] = w[1] * gd[5] - w[2] * gd[4];
+    gd[1] = w[2] * gd[3] - w[0] * gd[5];
+    gd[2] = w[0] * gd[4] - w[1] * gd[3];
+    int h = 2;
+#pragma unroll
+    for (int f = 0; f < 6; ++f)
+#pragma unroll
+      for (int g = f; g < 6; ++g) v[h++] += g < 3 ? Cm[f][g] : f < 3 ? Bm[f][g - 3] : A[f - 3][g - 3];
+#pragma unroll
+    for (int f = 0; f < 6; ++f) v[23 + f] += gd[f];
+    if constexpr (Base::kWeighted) v[kSums - 1] += wt;
   }
 };
 

@@ -2,7 +2,7 @@
 // loop of Open3D's registration_icp with TransformationEstimationPointToPlane, restated from the maths, beside the
 // point-to-point form of icp.hip.  The search, the loop with its stopping rule, the 6 x 6 solve and the update of T
 // are icp_core.hpp's (the nearest target point, strict < max_dist, the lowest row on a tie, fitness and rmse on
-// Euclidean distances); this file's own is what an evaluation sums.
+// Euclidean distances); what an evaluation sums is icp_core.hpp's PointToPlaneT, shared with icp_robust.hip.
 //
 // Per match, in registers: of a = [(q - c) x n, n], b = (q - y) . n (n the normal of the match y, c the target
 // fragment's first point) the upper triangle of sum a a^T (21) and sum a b (6).  Lane 0 solves xi = -H^-1 g from
@@ -19,24 +19,7 @@ namespace mvr {
 #endif
 constexpr int kPlaneThreads = MVR_ICP_PLANE_THREADS;
 
-struct PointToPlane : SixDofModel {   // the sums: n, sum d^2, upper triangle of sum a a^T [21], sum a b [6]
-  __device__ __forceinline__ static void accumulate(const IcpArgs& a, const double* sT, const double* sC,
-                                                    double (&v)[kSums], int64_t i, int64_t bt, const double (&q)[3]) {
-    const double n[3] = {a.normals[3 * bt], a.normals[3 * bt + 1], a.normals[3 * bt + 2]};
-    const double e[3] = {q[0] - a.xyz[3 * bt], q[1] - a.xyz[3 * bt + 1], q[2] - a.xyz[3 * bt + 2]};
-    const double w[3] = {q[0] - sC[0], q[1] - sC[1], q[2] - sC[2]};
-    const double ja[6] = {w[1] * n[2] - w[2] * n[1], w[2] * n[0] - w[0] * n[2], w[0] * n[1] - w[1] * n[0],
-                          n[0], n[1], n[2]};
-    const double b = e[0] * n[0] + e[1] * n[1] + e[2] * n[2];
-    int h = 2;
-#pragma unroll
-    for (int f = 0; f < 6; ++f)
-#pragma unroll
-      for (int g = f; g < 6; ++g) v[h++] += ja[f] * ja[g];
-#pragma unroll
-    for (int f = 0; f < 6; ++f) v[23 + f] += ja[f] * b;
-  }
-};
+using PointToPlane = PointToPlaneT<UnitWeight>;   // icp_core.hpp
 
 __global__ __launch_bounds__(kPlaneThreads) void icp_plane_kernel(IcpArgs a) {
   icp_loop<PointToPlane, kPlaneThreads>(a);

@@ -120,6 +120,10 @@ _SIGS = {
     "mvr_icp_refine_generalized": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp,
                                            c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double,
                                            ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mvr_icp_refine_robust": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp,
+                                      c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_int,
+                                      ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp]),
     "mvr_pair_information": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_int,
                                      ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mvr_compute_fpfh_workspace_bytes": (c_size, [c_i64]),

@@ -1,13 +1,15 @@
 """Fine registration: batched ICP on the fragments' own points, point-to-point (csrc/icp.hip mvr_icp_refine,
 DESIGN.md 4.19), point-to-plane on normals (csrc/icp_plane.hip mvr_icp_refine_plane) or generalized,
 plane-to-plane, on both fragments' normals (csrc/icp_gicp.hip mvr_icp_refine_generalized); the
-semantics are in include/mvreg.h.
+semantics are in include/mvreg.h.  Each of the three takes a robust kernel (`kernel`, `kernel_k`: csrc/icp_robust.hip
+mvr_icp_refine_robust), which weighs every correspondence by its residual in the solve.
 
 The reference stops at the coarse estimate (Procrustes or RANSAC over the sampled correspondences); its users
 follow it with Open3D's `registration_icp`.  `icp_refine` does that for every pair of a scene in one launch, on the
 radius index a `FragmentOverlap` already holds; `icp_pair` keeps the one-pair shape of `registration_icp`.
 `gicp_refine` and `gicp_pair` are the same two shapes for `registration_generalized_icp`.  Restated from the maths
-and pinned to tests/icp_oracle.py, tests/icp_plane_oracle.py and tests/gicp_oracle.py: Open3D parity is unpinned.
+and pinned to tests/icp_oracle.py, tests/icp_plane_oracle.py, tests/gicp_oracle.py and tests/icp_robust_oracle.py:
+Open3D parity is unpinned.
 
 Convention: T maps source coordinates into the target's frame, x_target ~ R x_source + t (rot_est / trans_est of
 filter_correspondences, the input of lib.multiview.synchronize) — the inverse of the `trans` of
@@ -18,8 +20,12 @@ import torch
 from lib import _native as N
 
 STATUS_FEW_CORRESPONDENCES, STATUS_ITERATION_CAP, STATUS_INVALID_PAIR = 1, 2, 4
-STATUS_DEGENERATE = 8     # not point-to-point: the 6 x 6 system is not positive definite to working precision
+# the 6 x 6 system is not positive definite to working precision; point-to-point: only with a robust kernel, when the
+# weights of the correspondences do not sum to more than 0 (every residual beyond Tukey's k)
+STATUS_DEGENERATE = 8
 METHODS = ("point_to_point", "point_to_plane")
+ROBUST_KERNELS = ("l2", "huber", "cauchy", "gm", "tukey")       # MVR_KERNEL_*: the index is the C constant
+_METHOD_IDS = {"point_to_point": 0, "point_to_plane": 1, "generalized": 2}                  # MVR_ICP_*
 
 
 def _check_settings(name, max_dist, max_iters, tol_fitness, tol_rmse):
@@ -39,6 +45,23 @@ def _check_method(name, method):
 def _check_epsilon(name, epsilon):
     if not 0.0 < epsilon <= 1.0:
         raise ValueError("%s: epsilon must lie in (0, 1]" % name)
+
+
+def _check_kernel(name, kernel, kernel_k, return_weight_sum=False):
+    """-> None for the plain entry, or (MVR_KERNEL_* id, k) for mvr_icp_refine_robust"""
+    if kernel is None:
+        if kernel_k is not None:
+            raise ValueError("%s: kernel_k needs a kernel" % name)
+        if return_weight_sum:
+            raise ValueError("%s: return_weight_sum needs a kernel ('l2' gives the count)" % name)
+        return None
+    if kernel not in ROBUST_KERNELS:
+        raise ValueError("%s: kernel must be one of %s, not %r" % (name, ", ".join(ROBUST_KERNELS), kernel))
+    if kernel == "l2":
+        return 0, 0.0 if kernel_k is None else float(kernel_k)
+    if kernel_k is None or not float(kernel_k) > 0.0:
+        raise ValueError("%s: kernel %r needs a positive kernel_k" % (name, kernel))
+    return ROBUST_KERNELS.index(kernel), float(kernel_k)
 
 
 def _run(name, fo, pairs, T_in, T_name, max_dist, needs_normals, call, normals_for=""):
@@ -75,9 +98,10 @@ def _run(name, fo, pairs, T_in, T_name, max_dist, needs_normals, call, normals_f
 
 
 def _refine(name, fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace, entry, needs_normals,
-            normals_for="", epsilon=None):
+            normals_for="", epsilon=None, robust=None, return_weight_sum=False):
     """icp_refine and gicp_refine after their own checks: entry names the C function, which takes the normals when
-    needs_normals and epsilon when that is not None."""
+    needs_normals and epsilon when that is not None.  robust (_check_kernel's pair) not None: mvr_icp_refine_robust as
+    the method `entry` names, with w_sum when return_weight_sum."""
     def call(P, ij, T0):
         dev = fo.device
         T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
@@ -87,14 +111,26 @@ def _refine(name, fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse,
         head = (N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz)) + \
             ((N.ptr(fo.normals),) if needs_normals else ()) + (N.ptr(fo.off_dev), fo.B, fo.M)
         eps = () if epsilon is None else (float(epsilon),)
-        N.check(getattr(N.lib(), entry)(*head, fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, *eps, int(max_iters),
-                                        float(tol_fitness), float(tol_rmse), N.ptr(T), N.ptr(fitness), N.ptr(rmse),
-                                        N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.stream()), entry)
+        if robust is None:
+            N.check(getattr(N.lib(), entry)(*head, fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, *eps, int(max_iters),
+                                            float(tol_fitness), float(tol_rmse), N.ptr(T), N.ptr(fitness),
+                                            N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace),
+                                            N.stream()), entry)
+        else:
+            w_sum = torch.empty(P, dtype=torch.float64, device=dev) if return_weight_sum else None
+            N.check(N.lib().mvr_icp_refine_robust(
+                N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals) if needs_normals else None,
+                N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(ij), N.ptr(T0), P, _METHOD_IDS[entry], max_dist,
+                1.0 if epsilon is None else float(epsilon), robust[0], robust[1], int(max_iters), float(tol_fitness),
+                float(tol_rmse), N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status),
+                N.ptr(trace), N.ptr(w_sum), N.stream()), "mvr_icp_refine_robust")
         T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
         T4[:, :3], T4[:, 3, 3] = T, 1.0
         out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
         if return_trace:
             out["trace"] = trace
+        if robust is not None and return_weight_sum:
+            out["w_sum"] = w_sum
         return out
     return _run(name, fo, pairs, T_init, "T_init", max_dist, needs_normals, call, normals_for)
 
@@ -126,7 +162,7 @@ def _pair_overlap(name, src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_r
 
 
 def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, return_trace=False,
-               method="point_to_point"):
+               method="point_to_point", kernel=None, kernel_k=None, return_weight_sum=False):
     """Refine the transform of every pair on the points of `fo` (a lib.overlap.FragmentOverlap: its centroids for
     method 'FCGF', its raw points for '3DMatch').
 
@@ -135,6 +171,11 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     and rmse both change by less than their tolerances (absolute); both tolerances 0 run exactly max_iters.
     method 'point_to_plane' minimises the distances along the target's normals instead: fo.normals (fp64 [M,3] on the
     device, from fo.estimate_normals() or assigned by the caller) must be there; their sign does not matter.
+    kernel: one of ROBUST_KERNELS, with its scale kernel_k > 0 in the unit of the residual (metres; 'gm': metres
+    squared; 'l2' takes none).  Every correspondence then enters the solve with the weight w(r) of its residual
+    (include/mvreg.h mvr_icp_refine_robust): the distance, or for 'point_to_plane' the distance along the normal.
+    Fitness, rmse, n_corr and the stopping rule stay unweighted.  return_weight_sum adds fp64 w_sum [P], the weights'
+    sum at the returned T.  None: the plain loop, every weight 1.
     Returns a dict of fp64 T [P,4,4], fp64 fitness / rmse [P], int32 n_corr / iters / status [P] (STATUS_* bits) and,
     with return_trace, fp64 trace [P, max_iters + 1, 2]: (fitness, rmse) of every evaluation, -1 after the last.
     The outputs stay on the device when T_init was on the device; otherwise they come back on the host (numpy for
@@ -142,7 +183,11 @@ def icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6,
     max_dist = float(fo.r if max_dist is None else max_dist)
     _check_settings("icp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
     _check_method("icp_refine", method)
+    robust = _check_kernel("icp_refine", kernel, kernel_k, return_weight_sum)
     plane = method == "point_to_plane"
+    if robust is not None:
+        return _refine("icp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
+                       method, plane, "method 'point_to_plane' ", robust=robust, return_weight_sum=return_weight_sum)
     return _refine("icp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
                    "mvr_icp_refine_plane" if plane else "mvr_icp_refine", plane, "method 'point_to_plane' ")
 
@@ -198,12 +243,14 @@ def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="p
     """One pair in the shape of Open3D's registration_icp(source, target, max_correspondence_distance, init):
     src_xyz [n,3], tgt_xyz [m,3], T_init [4,4] or [3,4] with x_target ~ T x_source.  voxel_size None: the raw points;
     a value: Open3D-style voxel centroids of both clouds (lib.overlap).  **kw: max_iters, tol_fitness, tol_rmse,
-    return_trace of icp_refine.  method 'point_to_plane': the normals are estimated here over normal_radius (None:
-    max_dist) on an index of cell max(max_dist, normal_radius); TransformationEstimationPointToPlane after
+    return_trace, kernel, kernel_k, return_weight_sum of icp_refine.  method 'point_to_plane': the normals are
+    estimated here over normal_radius (None: max_dist) on an index of cell max(max_dist, normal_radius);
+    TransformationEstimationPointToPlane after
     estimate_normals(KDTreeSearchParamRadius(normal_radius)).  Returns icp_refine's dict without the leading [P]."""
     _check_settings("icp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
                     kw.get("tol_rmse", 0.0))
     _check_method("icp_pair", method)
+    _check_kernel("icp_pair", kw.get("kernel"), kw.get("kernel_k"), kw.get("return_weight_sum", False))
     fo, T0 = _pair_overlap("icp_pair", src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius,
                            method == "point_to_plane")
     out = icp_refine(fo, [[0, 1]], T0, max_dist, method=method, **kw)
@@ -211,17 +258,23 @@ def icp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, method="p
 
 
 def gicp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6, epsilon=1e-3,
-                return_trace=False):
+                return_trace=False, kernel=None, kernel_k=None, return_weight_sum=False):
     """Generalized (plane-to-plane) ICP on every pair of `fo`: icp_refine's arguments, conventions, stopping rule and
     dict, with the solve of Segal et al.'s GICP (Open3D's registration_generalized_icp; parity unpinned).
 
     Every point's covariance is 1 in its surface and `epsilon` along its normal, so both fragments' surfaces weigh a
     residual.  fo.normals (fp64 [M,3] on the device, from fo.estimate_normals() or assigned by the caller) must be
     there and unit: they are not renormalised, their sign does not matter.  epsilon in (0, 1]; 1 makes the normals
-    drop out.  status bit STATUS_DEGENERATE as for 'point_to_plane'."""
+    drop out.  status bit STATUS_DEGENERATE as for 'point_to_plane'.  kernel, kernel_k, return_weight_sum: as
+    icp_refine's, on the residual sqrt(d^T A d) (d = q - y, A the inverse of the pair's summed covariances: a distance
+    in which the surfaces' own directions count half, so roughly metres)."""
     max_dist = float(fo.r if max_dist is None else max_dist)
     _check_settings("gicp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
     _check_epsilon("gicp_refine", epsilon)
+    robust = _check_kernel("gicp_refine", kernel, kernel_k, return_weight_sum)
+    if robust is not None:
+        return _refine("gicp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
+                       "generalized", True, epsilon=epsilon, robust=robust, return_weight_sum=return_weight_sum)
     return _refine("gicp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
                    "mvr_icp_refine_generalized", True, epsilon=epsilon)
 
@@ -229,11 +282,12 @@ def gicp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6
 def gicp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, normal_radius=None, epsilon=1e-3, **kw):
     """One pair in the shape of Open3D's registration_generalized_icp(source, target, max_correspondence_distance,
     init): icp_pair's arguments.  The normals of both clouds are estimated here over normal_radius (None: max_dist) on
-    an index of cell max(max_dist, normal_radius).  **kw: max_iters, tol_fitness, tol_rmse, return_trace of
-    gicp_refine.  Returns gicp_refine's dict without the leading [P]."""
+    an index of cell max(max_dist, normal_radius).  **kw: max_iters, tol_fitness, tol_rmse, return_trace, kernel,
+    kernel_k, return_weight_sum of gicp_refine.  Returns gicp_refine's dict without the leading [P]."""
     _check_settings("gicp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
                     kw.get("tol_rmse", 0.0))
     _check_epsilon("gicp_pair", epsilon)
+    _check_kernel("gicp_pair", kw.get("kernel"), kw.get("kernel_k"), kw.get("return_weight_sum", False))
     fo, T0 = _pair_overlap("gicp_pair", src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, True)
     out = gicp_refine(fo, [[0, 1]], T0, max_dist, epsilon=epsilon, **kw)
     return {k: v[0] for k, v in out.items()}

@@ -533,7 +533,8 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
                    dataset="3d_match", overlap_threshold=None, normal_radius=None, fpfh_radius=None, seed=0,
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
                    min_frags=1, min_points=1, ransac_checkers=False, line_process=False,
-                   preference_loop_closure=1.0, denoise=None, coarse="ransac", keypoints=None):
+                   preference_loop_closure=1.0, denoise=None, coarse="ransac", keypoints=None, icp_kernel=None,
+                   icp_kernel_k=None):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
@@ -555,7 +556,9 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
       5. the overlap gate of the pairwise benchmark: a pair is kept when FragmentOverlap.ratios >= overlap_threshold
          (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
       6. lib.icp.icp_refine (method 'point_to_point' / 'point_to_plane') or gicp_refine ('generalized') on the kept
-         pairs;  7. lib.icp.information_matrix;  8. synchronize(irls_iters=5);  9. optimize_pose_graph with the
+         pairs; icp_kernel (None: every correspondence weighs 1, the chain and the result as without it): one of
+         lib.icp.ROBUST_KERNELS with its scale icp_kernel_k, None: voxel_size, the sampling scale of the centroids
+         (a documented default, not a tuned value; 'gm' takes a squared length, so give it one);  7. lib.icp.information_matrix;  8. synchronize(irls_iters=5);  9. optimize_pose_graph with the
          IRLS weights (line_process: with Open3D's line process and edge pruning, every kept pair an uncertain edge,
          preference_loop_closure, and the distance the information matrices used: icp_max_dist, None: the index's
          cell);  10. fuse_scene(voxel fuse_voxel, None: voxel_size) over the fragments connected to `anchor`.
@@ -568,7 +571,7 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     points each fragment lost); with keypoints also keypoints: rows [K] (rows of fo.xyz, ascending) and off [n+1]
     (numpy int64)."""
     from lib.fpfh import register_fgr, register_fpfh
-    from lib.icp import gicp_refine, icp_refine, information_matrix
+    from lib.icp import _check_kernel, gicp_refine, icp_refine, information_matrix
     from lib.overlap import FragmentOverlap
     n = len(xyz_list)
     if coarse not in COARSE_METHODS:
@@ -576,6 +579,10 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     if coarse == "fgr" and ransac_checkers is not False:
         raise ValueError("register_scene: ransac_checkers belongs to coarse='ransac', not to coarse='fgr'")
     pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints)
+    if icp_kernel is not None and icp_kernel_k is None:
+        icp_kernel_k = float(voxel_size)
+    _check_kernel("register_scene", icp_kernel, icp_kernel_k)
+    robust = {} if icp_kernel is None else {"kernel": icp_kernel, "kernel_k": icp_kernel_k}
     denoise = _denoise_arguments(denoise, 3.0 * float(voxel_size))
     keypoints = _keypoints_arguments(keypoints, 3.0 * float(voxel_size), init)
     threshold = OVERLAP_THRESHOLDS[dataset] if overlap_threshold is None else float(overlap_threshold)
@@ -611,9 +618,10 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     kept = overlap >= threshold
     kp = pairs[kept]
     if method == "generalized":
-        ref = gicp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, epsilon=gicp_epsilon)
+        ref = gicp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, epsilon=gicp_epsilon,
+                          **robust)
     else:
-        ref = icp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, method=method)
+        ref = icp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, method=method, **robust)
     Tk = np.asarray(ref["T"], dtype=np.float64).reshape(-1, 4, 4)
     info = information_matrix(fo, kp, Tk, max_dist=icp_max_dist)
     sync = synchronize(Tk[:, :3, :3], Tk[:, :3, 3], kp, n, anchor=anchor, irls_iters=5)

@@ -14,11 +14,13 @@ gate is an uncertain edge); the pairs it pruned are counted in the printed line.
 before anything else uses them; the points removed per fragment are printed.
 --keypoints iss[:SALIENT:NONMAX]: ISS keypoints (Open3D's compute_iss_keypoints; radii default to 3 and 2 voxel sizes)
 are detected on each fragment and the FPFH matching runs on them alone; the keypoints per fragment are printed.
+--icp_kernel huber|cauchy|gm|tukey|l2[:K]: the ICP stage weighs every correspondence by a robust kernel of scale K
+(K defaults to the voxel size; lib.icp.ROBUST_KERNELS); the kernel and its scale are printed.
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
            [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
            [--checkers | --coarse fgr] [--line_process [--preference_loop_closure 1.0]] [--denoise statistical:20:2.0]
-           [--keypoints iss[:SALIENT:NONMAX]]
+           [--keypoints iss[:SALIENT:NONMAX]] [--icp_kernel tukey[:K]]
 """
 import argparse
 import os
@@ -37,6 +39,7 @@ from scripts.multiview_sync import write_poses  # noqa: E402
 ICP_METHODS = ("point_to_point", "point_to_plane", "generalized")   # lib.multiview.ICP_METHODS
 DATASETS = ("3d_match", "redwood")                                  # lib.multiview.OVERLAP_THRESHOLDS
 COARSE_METHODS = ("ransac", "fgr")                                  # lib.multiview.COARSE_METHODS
+ROBUST_KERNELS = ("l2", "huber", "cauchy", "gm", "tukey")           # lib.icp.ROBUST_KERNELS
 
 
 def read_init(filename, n_fragments):
@@ -82,6 +85,22 @@ def parse_keypoints(text):
     return d
 
 
+def parse_icp_kernel(text):
+    """'NAME' or 'NAME:K' -> (name, K or None) of register_scene's icp_kernel / icp_kernel_k (ValueError on anything
+    else)"""
+    parts = text.split(":")
+    try:
+        if parts[0] not in ROBUST_KERNELS or len(parts) > 2:
+            raise ValueError("neither form")
+        k = float(parts[1]) if len(parts) == 2 else None
+        if k is not None and not k > 0.0:
+            raise ValueError("K not positive")
+    except ValueError:
+        raise ValueError("--icp_kernel must be NAME or NAME:K with NAME one of %s and K > 0, not %r"
+                         % (", ".join(ROBUST_KERNELS), text))
+    return parts[0], k
+
+
 def parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--fragments", required=True, nargs="+", help="the fragments' PLY files (at least two)")
@@ -110,6 +129,9 @@ def parser():
                     help="match the FPFH descriptors of ISS keypoints only: iss, or iss:SALIENT:NONMAX (Open3D's "
                          "compute_iss_keypoints radii, each at most 3 voxel_size; defaults 3 and 2 voxel_size); not "
                          "with --init")
+    ap.add_argument("--icp_kernel", default=None, metavar="NAME[:K]",
+                    help="weigh the ICP correspondences by a robust kernel: huber, cauchy, gm, tukey or l2, with its "
+                         "scale K (Open3D's RobustKernel; K defaults to the voxel size, for gm a squared length)")
     return ap
 
 
@@ -138,6 +160,11 @@ def check_args(ap, a):
             a.keypoints = _keypoints_arguments(parse_keypoints(a.keypoints), 3.0 * a.voxel_size, a.init)
         except ValueError as e:
             ap.error(str(e))
+    if a.icp_kernel is not None:
+        try:
+            a.icp_kernel = parse_icp_kernel(a.icp_kernel)
+        except ValueError as e:
+            ap.error(str(e))
     return a
 
 
@@ -153,7 +180,9 @@ def main(argv=None):
                          **({} if not a.line_process else dict(line_process=True,
                                                                preference_loop_closure=a.preference_loop_closure)),
                          **({} if a.denoise is None else dict(denoise=a.denoise)),
-                         **({} if a.keypoints is None else dict(keypoints=a.keypoints)))
+                         **({} if a.keypoints is None else dict(keypoints=a.keypoints)),
+                         **({} if a.icp_kernel is None else dict(icp_kernel=a.icp_kernel[0],
+                                                                 icp_kernel_k=a.icp_kernel[1])))
     ensure_dir(a.out)
     write_poses(res["poses"], os.path.join(a.out, "poses.txt"))
     rec = res["pairs"]
@@ -172,6 +201,8 @@ def main(argv=None):
               % (a.denoise["method"], " ".join(str(int(v)) for v in res["denoise"]["removed"])))
     if a.keypoints is not None:
         print("keypoints (iss): per fragment: %s" % " ".join(str(int(v)) for v in np.diff(res["keypoints"]["off"])))
+    if a.icp_kernel is not None:
+        print("icp kernel: %s, k %g" % (a.icp_kernel[0], a.voxel_size if a.icp_kernel[1] is None else a.icp_kernel[1]))
     if a.line_process:
         print("line process: %d of the %d gated pairs pruned" % (int(rec["pruned"].sum()), int(rec["kept"].sum())))
     return res

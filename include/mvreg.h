@@ -527,6 +527,59 @@ int mvr_icp_refine_generalized(const void* index, size_t index_bytes, const doub
                                int32_t* n_corr, int32_t* iters, int32_t* status, double* trace, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Robust kernels on the three ICP variants, batched over pairs (csrc/icp_robust.hip): what Open3D's
+ * RobustKernel does to registration_icp and registration_generalized_icp, restated from the maths; Open3D parity is
+ * unpinned.  The arguments are those of mvr_icp_refine_generalized plus method, kernel, kernel_k and w_sum.
+ *   method: MVR_ICP_POINT_TO_POINT (mvr_icp_refine), MVR_ICP_POINT_TO_PLANE (mvr_icp_refine_plane),
+ *   MVR_ICP_GENERALIZED (mvr_icp_refine_generalized).  normals may be NULL for point-to-point; epsilon is looked at
+ *   for generalized only.
+ *   kernel, with r the residual of a valid correspondence and k = kernel_k > 0 the kernel's scale:
+ *     MVR_KERNEL_L2      w = 1
+ *     MVR_KERNEL_HUBER   w = k / max(|r|, k)
+ *     MVR_KERNEL_CAUCHY  w = 1 / (1 + (r / k)^2)
+ *     MVR_KERNEL_GM      w = k / (k + r^2)^2
+ *     MVR_KERNEL_TUKEY   w = (1 - (r / k)^2)^2 for |r| <= k, else 0
+ *   All are continuous in r, Tukey's at |r| == k too.  L1 is not built: its weight 1 / |r| is unbounded at r = 0.
+ *   kernel_k is not looked at for L2.
+ *   Point-to-point: r = |q - y| (the distance of the search).  The solve is the weighted Kabsch solution on the
+ *   original source points: with W = sum w the means sum w x / W and sum w y / W, the covariance
+ *   sum w x y^T - W m_x m_y^T, and mvr_icp_refine's per-pair origins, SVD and det correction.  If W > 0 fails (a NaN
+ *   fails it too) the loop ends with status bit 8, T kept, iters not counted: bit 8 exists for this method through
+ *   this entry only.
+ *   Point-to-plane: r = b = (q - y) . n;  H = sum w a a^T, g = sum w a b, with a, b, c and the Cholesky pivot rule of
+ *   mvr_icp_refine_plane.  All-zero weights fail the first pivot: bit 8.
+ *   Generalized: r = sqrt(d^T A d), d = q - y and A = M^-1 of mvr_icp_refine_generalized (a negative rounding of
+ *   d^T A d counts as 0);  H = sum w G^T A G, g = sum w G^T A d.
+ *   The weights of a solve are evaluated at the T the solve starts from: one step of iteratively reweighted least
+ *   squares per ICP iteration, as Open3D does.  eval(T), fitness, rmse, n_corr, the stopping rule, the trace, the
+ *   status bits 1, 2 and 4 and the least correspondence counts (3 / 6 / 6, on the unweighted count) are exactly those
+ *   of the method's own entry: weights enter the solve only, so the figures compare across kernels.
+ *   MVR_KERNEL_L2 returns, for each method, T, fitness, rmse, n_corr, iters, status and trace bit-identical to the
+ *   method's own entry (a weight of exactly 1.0 in the same products).
+ *   w_sum [P] (may be NULL): sum w over the valid correspondences of the returned T's evaluation; with L2 that equals
+ *   n_corr; 0 for an invalid pair.
+ *   fp64 throughout; one workgroup per pair, every iteration inside the one launch, no atomics, no workspace, the
+ *   reduction in a fixed order; a pair's outputs are a function of the pair alone.
+ *   MVR_EINVAL, scalars first: the rules of the method's own entry (epsilon for generalized only); a method or a
+ *   kernel outside its range; for a kernel other than L2 a kernel_k that is not > 0 (a NaN included).  P == 0 then
+ *   returns MVR_OK.  With P > 0 and M > 0 a NULL normals for the two methods that use them.
+ * ---------------------------------------------------------------------- */
+#define MVR_ICP_POINT_TO_POINT 0
+#define MVR_ICP_POINT_TO_PLANE 1
+#define MVR_ICP_GENERALIZED 2
+#define MVR_KERNEL_L2 0
+#define MVR_KERNEL_HUBER 1
+#define MVR_KERNEL_CAUCHY 2
+#define MVR_KERNEL_GM 3
+#define MVR_KERNEL_TUKEY 4
+int mvr_icp_refine_robust(const void* index, size_t index_bytes, const double* xyz, const double* normals,
+                          const int64_t* off, int B, int64_t M, double r_index, const int64_t* pairs, const double* T0,
+                          int P, int method, double max_dist, double epsilon, int kernel, double kernel_k,
+                          int max_iters, double tol_fitness, double tol_rmse, double* T, double* fitness, double* rmse,
+                          int32_t* n_corr, int32_t* iters, int32_t* status, double* trace, double* w_sum,
+                          mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Per-pair 6 x 6 information matrices on a radius index (csrc/info.hip): what Open3D's
  * get_information_matrix_from_point_clouds gives a pose-graph edge, restated from the maths.
  * The arguments are those of mvr_icp_refine without the loop settings; T [P,12] (3x4 row-major) is evaluated as it

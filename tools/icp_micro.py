@@ -7,12 +7,14 @@ mvr_radius_overlap_count call on the same index (one 27-cell walk with early exi
 the host oracle (tests/icp_oracle.py: sklearn kd-tree + numpy SVD) on the first --host_pairs pairs.  HIP events around
 each call after a warm-up, median over --reps calls.  point_to_plane and generalized also time the normal estimation
 (radius = the cell; generalized takes --epsilon), and every method reports the iterations to convergence at
-tolerances 1e-6 from the same starts.
+tolerances 1e-6 from the same starts.  --kernel NAME[:K] sends the same calls through csrc/icp_robust.hip
+mvr_icp_refine_robust with that robust kernel (l2, huber, cauchy, gm, tukey; K defaults to the voxel size): l2 against
+a run without the flag is what the weighted path costs, tukey against l2 what a kernel costs.
 A library built with another workgroup size (tools/build_variant.sh icp.hip icp512 -DMVR_ICP_THREADS=512, or
 icp_plane.hip plane512 -DMVR_ICP_PLANE_THREADS=512, icp_gicp.hip gicp512 -DMVR_ICP_GICP_THREADS=512, normals.hip
 nrm256 -DMVR_NORMALS_THREADS=256; MVR_LIB=tools/vsp/icp512.so) times that variant.
 usage: python tools/icp_micro.py [--method point_to_point|point_to_plane|generalized] [--epsilon 1e-3] [--frags 30]
-                                 [--reps 7] [--host_pairs 4]"""
+                                 [--reps 7] [--host_pairs 4] [--kernel tukey:0.025]"""
 import argparse
 import os
 import sys
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--host_pairs", type=int, default=4)
     ap.add_argument("--method", default="point_to_point", choices=["point_to_point", "point_to_plane", "generalized"])
     ap.add_argument("--epsilon", type=float, default=1e-3)
+    ap.add_argument("--kernel", default=None, metavar="NAME[:K]")
     a = ap.parse_args()
     d = torch.device("cuda")
     frags, poses = synth_scene_fragments(n_frag=a.frags)
@@ -72,6 +75,12 @@ def main():
         return ms
 
     plane, gicp = a.method == "point_to_plane", a.method == "generalized"
+    nrm = None
+    if a.kernel is not None:
+        from lib.icp import ROBUST_KERNELS
+        name, _, k = a.kernel.partition(":")
+        kernel, kernel_k = ROBUST_KERNELS.index(name), float(k) if k else 0.025
+        print("through mvr_icp_refine_robust: kernel %s, k %g" % (name, kernel_k), flush=True)
     if plane or gicp:
         nrm = torch.empty(fo.M, 3, dtype=torch.float64, device=d)
         nnb = torch.empty(fo.M, dtype=torch.int32, device=d)
@@ -94,7 +103,13 @@ def main():
                 N.ptr(it), N.ptr(st), None, N.stream())
 
         def run():
-            if gicp:
+            if a.kernel is not None:
+                assert L.mvr_icp_refine_robust(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
+                                               N.ptr(fo.off_dev), fo.B, fo.M, *tail[:4],
+                                               ["point_to_point", "point_to_plane", "generalized"].index(a.method),
+                                               tail[4], a.epsilon, kernel, kernel_k, *tail[5:-1], None,
+                                               tail[-1]) == 0
+            elif gicp:
                 assert L.mvr_icp_refine_generalized(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
                                                     N.ptr(fo.off_dev), fo.B, fo.M, *tail[:5], a.epsilon,
                                                     *tail[5:]) == 0
