@@ -57,30 +57,6 @@ __device__ __forceinline__ double block_max(double v, double* red) {
   return m;
 }
 
-// check 2 of mvr_ransac_checked on rows a, b: rounded fp64 operations, no fma
-__device__ __forceinline__ bool fgr_edge_ok(const double* x1, const double* x2, int64_t a, int64_t b, double s2) {
-#pragma clang fp contract(off)
-  const double s0 = x1[3 * a] - x1[3 * b], s1 = x1[3 * a + 1] - x1[3 * b + 1], sz = x1[3 * a + 2] - x1[3 * b + 2];
-  const double t0 = x2[3 * a] - x2[3 * b], t1 = x2[3 * a + 1] - x2[3 * b + 1], tz = x2[3 * a + 2] - x2[3 * b + 2];
-  const double ls2 = (s0 * s0 + s1 * s1) + sz * sz;
-  const double lt2 = (t0 * t0 + t1 * t1) + tz * tz;
-  return ls2 >= s2 * lt2 && lt2 >= s2 * ls2;
-}
-
-// |T x1_i - x2_i|^2 in the operation order of ransac_eval_kernel (oracle/ransac.py evaluate): rounded ops, no fma
-__device__ __forceinline__ double fgr_row_d2(const double* sT, const double* x1, const double* x2, int64_t i) {
-#pragma clang fp contract(off)
-  const double a = x1[3 * i], b = x1[3 * i + 1], c = x1[3 * i + 2];
-  double dd = 0.0;
-#pragma unroll
-  for (int e = 0; e < 3; ++e) {
-    const double y = ((sT[4 * e] * a + sT[4 * e + 1] * b) + sT[4 * e + 2] * c) + sT[4 * e + 3];
-    const double df = y - x2[3 * i + e];
-    dd = dd + df * df;
-  }
-  return dd;
-}
-
 template <int kThreads>
 __device__ __forceinline__ void fgr_pair(const FgrArgs& a) {
   constexpr int kWaves = kThreads / 64;
@@ -157,6 +133,9 @@ __device__ __forceinline__ void fgr_pair(const FgrArgs& a) {
   };
 
   // ---- 2. the used rows
+  auto edge_ok = [&](int64_t i, int64_t j) {   // check 2 of mvr_ransac_checked on rows i, j
+    return ransac_edge_ok(x1 + 3 * i, x1 + 3 * j, x2 + 3 * i, x2 + 3 * j, a.s2);
+  };
   int n_tuples = 0, m = n;
   if (a.tuple_factor > 0) {   // uniform
     const int64_t total = (int64_t)a.tuple_factor * n;   // < 2^31 (checked by the entry point)
@@ -166,15 +145,9 @@ __device__ __forceinline__ void fgr_pair(const FgrArgs& a) {
       int64_t c[3] = {0, 0, 0};
       bool ok = it < total;
       if (ok) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const uint64_t ctr = ((uint64_t)p << 40) | ((uint64_t)it << 8) | (uint64_t)j;
-          c[j] = (int64_t)(ransac_draw(a.seed, ctr) % (uint64_t)n);
-        }
+        ransac_draws(a.seed, p, (uint64_t)it, n, 3, c);
         ok = c[0] != c[1] && c[0] != c[2] && c[1] != c[2];
-        if (ok)
-          ok = fgr_edge_ok(x1, x2, c[0], c[1], a.s2) && fgr_edge_ok(x1, x2, c[0], c[2], a.s2) &&
-               fgr_edge_ok(x1, x2, c[1], c[2], a.s2);
+        if (ok) ok = edge_ok(c[0], c[1]) && edge_ok(c[0], c[2]) && edge_ok(c[1], c[2]);
       }
       const unsigned long long mask = __ballot(ok);
       const int pre = __popcll(mask & ((1ull << lane) - 1ull));
@@ -268,7 +241,7 @@ __device__ __forceinline__ void fgr_pair(const FgrArgs& a) {
   const double d2max = a.max_dist * a.max_dist;
   double s[2] = {0.0, 0.0};
   for (int i = tid; i < n; i += kThreads) {
-    const double dd = fgr_row_d2(sT, x1, x2, i);
+    const double dd = ransac_row_d2<4, 4>(sT, sT + 3, x1 + 3 * (int64_t)i, x2 + 3 * (int64_t)i);
     if (dd < d2max) {
       s[0] += 1.0;
       s[1] += dd;

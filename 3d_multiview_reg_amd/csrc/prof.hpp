@@ -16,7 +16,7 @@ enum ProfKind : int {
   PK_SPCONV = 8,     // FCGF sparse conv
   PK_SPARSE_MISC = 9,
   PK_POINTCN = 10,   // fused PointCN (pointcn.hip)
-  PK_RANSAC_CHECK = 11,   // mvr_ransac_checked's four launches (ransac_checked.hip; tools/ransac_micro.py --checked)
+  PK_RANSAC_CHECK = 11,   // mvr_ransac_checked's four launches (ransac.hip; tools/ransac_micro.py --checked)
   PK_RANSAC_SCAN = 12,
   PK_RANSAC_EVAL = 13,
   PK_RANSAC_SELECT = 14,

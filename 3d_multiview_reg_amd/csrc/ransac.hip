@@ -1,9 +1,26 @@
-// RANSAC over given correspondences with correspondence checkers and a validation cap (mvr_ransac_checked;
-// include/mvreg.h has the semantics, DESIGN.md 4.26 the measurements).
+// RANSAC over given correspondences, batched over pairs: mvr_ransac, and mvr_ransac_checked with correspondence
+// checkers and a validation cap (include/mvreg.h has the semantics, DESIGN.md 4.26 the measurements).
 //
-// What Open3D's global-registration examples configure: 3-point samples, the edge-length (0.9), distance and
-// normal checkers, 100000 iterations, of which only the samples that pass every checker are scored against all
-// correspondences.  Scoring is the expensive step (n x ~27 fp64 ops per hypothesis); the checkers need the sample's
+// mvr_ransac: lib/utils.py:671-709 run_ransac ->
+// Open3D 0.9 registration_ransac_based_on_correspondence(TransformationEstimationPointToPoint(False),
+// ransac_n = 4, max_correspondence_distance = 0.05, RANSACConvergenceCriteria(50000, 2500)).
+// Open3D 0.9's loop (restated; oracle/ransac.py): min(max_iteration, max_validation) iterations; each draws
+// ransac_n correspondences with replacement, fits R, t by Umeyama without scaling (fp64), and scores the
+// fit over ALL correspondences: inlier iff |R x1 + t - x2|^2 < d^2, fitness = inliers / n,
+// rmse = sqrt(sum of inlier d^2 / inliers); the result is the first hypothesis that is best by (fitness
+// desc, rmse asc) among those with fitness > 0, identity when none (or n < ransac_n).  Open3D seeds
+// std::rand from the clock; here the draws are a counter stream over (seed, pair, iteration, draw)
+// (ransac.hpp ransac_draws) — reproducible, and the same on the host (oracle/ransac.py:draws).
+//
+// One thread per (pair, hypothesis): its draws, the Umeyama fit (jacobi_svd3), then a sequential pass
+// over the pair's correspondences staged through LDS in 256-row tiles (every thread of the workgroup reads
+// the same row: LDS broadcast), in correspondence order and with rounded fp64 ops (no contraction), so the
+// counts and error sums equal the host restatement's bit for bit.  A second kernel picks each pair's best.
+// Work per pair: iters x n x ~15 fp64 ops (2500 x 5000: 0.19 GFLOP) — fp64 VALU-bound.
+//
+// mvr_ransac_checked: what Open3D's global-registration examples configure: 3-point samples, the edge-length (0.9),
+// distance and normal checkers, 100000 iterations, of which only the samples that pass every checker are scored against
+// all correspondences.  Scoring is the expensive step (n x ~27 fp64 ops per hypothesis); the checkers need the sample's
 // own points only, so 40 times mvr_ransac's draws cost less than its 2500 evaluations.  No confidence-based early
 // exit: when to stop depends on each pair's running best, which a batched launch of all iterations does not have.
 //
@@ -18,14 +35,11 @@
 //                     word per wave (lane 0 stores it).
 //   rc_scan_kernel    one workgroup per pair: popcounts of the words, a prefix sum, and the ordered list of the first
 //                     max_validation passing iterations; n_pass, n_valid.
-//   rc_eval_kernel    one thread per validated hypothesis: re-derives it from its iteration id (draws + fit, dense),
-//                     exports it, and scores it exactly as ransac_eval_kernel (procrustes.hip) does: LDS tiles of
-//                     256 rows, sequential, rounded fp64 ops.  Workgroups beyond n_valid[p] exit at once.
-//   rc_select_kernel  ransac_select_kernel over the validated list (ascending iteration = ascending slot).
-//
-// The fit and the scoring loop restate ransac_eval_kernel's instead of sharing a function with it: mvr_ransac's
-// object code, which the reference's --refine / RANSAC paths are pinned to, stays what it was.  The anchor test
-// (tests/test_gpu_ransac_checked.py) holds the two byte-identical.
+//   ransac_eval_kernel<RansacListed>    one thread per validated hypothesis: re-derives it from its iteration id
+//                     (draws + fit, dense), exports it and scores it.  Workgroups beyond n_valid[p] exit at once.
+//   ransac_select_kernel<RansacListed>  the best of the validated list (ascending iteration = ascending slot).
+// mvr_ransac is the last two alone, as <RansacPlain>: every iteration is a slot of its own.  The two policies hold
+// all that the entries differ in there; the draws, the fit, the scoring loop and the order of the selection stand once.
 #include "common.hpp"
 #include "prof.hpp"
 #include "ransac.hpp"
@@ -37,27 +51,40 @@ namespace mvr {
 constexpr int RC_MAXN = 8;     // ransac_n <= 8
 constexpr int RC_TILE = 256;
 
-struct RcArgs {
+// (the fields stay in this order: with mvr_ransac's fields moved to the front rc_check_kernel, the same instructions
+// but for the kernel-argument offsets, measured 2.6 % slower, 5.08 against 4.95 ms — DESIGN.md 4.26)
+struct RansacArgs {
   const double* x1; const double* x2; int64_t ps;   // [P][ps] rows of 3 doubles
   const double* nrm1; const double* nrm2;           // both set or both null
-  const int32_t* n;
+  const int32_t* n;                                  // [P] correspondences per pair
   int P, iters, rn, maxv, nwords;
   int bpp, vpp;                                      // 256-thread blocks per pair: check, eval
-  double d2, sim2, cd2, ncos;
+  double d2, sim2, cd2, ncos;                        // max distance squared; the checkers' thresholds
   uint64_t seed;
   uint64_t* bits;                                    // [P][nwords]
   int32_t* n_pass; int32_t* n_valid;                 // [P]
-  int32_t* valid; int32_t* cnt; double* err;         // [P][maxv]
-  double* hyp;                                       // [P][maxv][12]
-};
+  int32_t* valid; int32_t* cnt; double* err;         // [P][maxv]; mvr_ransac: cnt, err [P][iters]
+  double* hyp;                                       // [P][maxv][12] (R row-major, t); mvr_ransac: [P][iters][12]
+};                                                   // mvr_ransac leaves the checkers' fields 0
 
-__device__ __forceinline__ void rc_draws(const RcArgs& a, int p, int it, int n, int64_t c[RC_MAXN]) {
-#pragma unroll
-  for (int j = 0; j < RC_MAXN; ++j) {
-    const uint64_t ctr = ((uint64_t)p << 40) | ((uint64_t)it << 8) | (uint64_t)j;
-    c[j] = j < a.rn ? (int64_t)(ransac_draw(a.seed, ctr) % (uint64_t)n) : 0;
+// What the evaluation and the selection of the two entries differ in: a pair's hypotheses sit in slots
+// 0 .. live - 1 of its rows of cnt / err / hyp, `stride` slots apart from the next pair's.
+struct RansacPlain {    // mvr_ransac: grid (blocks, pairs); slot = iteration, all of them live
+  static __device__ __forceinline__ int pair(const RansacArgs&) { return blockIdx.y; }
+  static __device__ __forceinline__ int block(const RansacArgs&) { return blockIdx.x; }
+  static __device__ __forceinline__ int live(const RansacArgs& a, int) { return a.iters; }
+  static __device__ __forceinline__ int iter(const RansacArgs&, int, int slot) { return slot; }
+  static __device__ __forceinline__ int stride(const RansacArgs& a) { return a.iters; }
+};
+struct RansacListed {   // mvr_ransac_checked: grid pairs x vpp, flattened; slot = index into the validated list
+  static __device__ __forceinline__ int pair(const RansacArgs& a) { return blockIdx.x / a.vpp; }
+  static __device__ __forceinline__ int block(const RansacArgs& a) { return blockIdx.x % a.vpp; }
+  static __device__ __forceinline__ int live(const RansacArgs& a, int p) { return a.n_valid[p]; }
+  static __device__ __forceinline__ int iter(const RansacArgs& a, int p, int slot) {
+    return a.valid[(int64_t)p * a.maxv + slot];
   }
-}
+  static __device__ __forceinline__ int stride(const RansacArgs& a) { return a.maxv; }
+};
 
 __device__ __forceinline__ void rc_load(const double* x, const int64_t c[RC_MAXN], int k, double v[RC_MAXN][3]) {
 #pragma unroll
@@ -66,7 +93,7 @@ __device__ __forceinline__ void rc_load(const double* x, const int64_t c[RC_MAXN
     for (int e = 0; e < 3; ++e) v[j][e] = j < k ? x[3 * c[j] + e] : 0.0;
 }
 
-// Umeyama without scaling on k sample points, ransac_eval_kernel's operations in its order:
+// Umeyama without scaling on k sample points (unrolled to RC_MAXN and predicated: no array is indexed at run time):
 // sigma = sum (dst - mu_d)(src - mu_s)^T / k = U S V^T, R = U diag(1, 1, sign(det U det V)) V^T, t = mu_d - R mu_s
 __device__ __forceinline__ void rc_fit(const double s[RC_MAXN][3], const double d[RC_MAXN][3], int k, double R[3][3],
                                        double t[3]) {
@@ -102,7 +129,34 @@ __device__ __forceinline__ void rc_fit(const double s[RC_MAXN][3], const double 
     t[r] = md[r] - ((R[r][0] * ms[0] + R[r][1] * ms[1]) + R[r][2] * ms[2]);
 }
 
-__global__ __launch_bounds__(256) void rc_check_kernel(RcArgs a) {
+// inliers and their error sum of (R, t) over the pair's n rows, in row order: the whole workgroup calls it and stages
+// the rows through `tile`
+__device__ __forceinline__ void rc_score(const double* x1, const double* x2, int n, const double R[3][3],
+                                         const double t[3], double d2, double (*tile)[6], int& good, double& e2) {
+#pragma clang fp contract(off)   // hipcc contracts a * b + c into fma by default; the evaluation rounds every op
+  int cnt = 0;          // locals: accumulated through the reference parameters, the two-row loop body carried a second
+  double err = 0.0;     // copy of the count (86 instructions for 79)
+  for (int b0 = 0; b0 < n; b0 += RC_TILE) {
+    const int nb = min(RC_TILE, n - b0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nb * 6; i += blockDim.x) {
+      const int r = i / 6, e = i % 6;
+      tile[r][e] = e < 3 ? x1[3 * (int64_t)(b0 + r) + e] : x2[3 * (int64_t)(b0 + r) + e - 3];
+    }
+    __syncthreads();
+    for (int r = 0; r < nb; ++r) {
+      const double dd = ransac_row_d2<3, 1>(&R[0][0], t, tile[r], tile[r] + 3);
+      if (dd < d2) {
+        ++cnt;
+        err = err + dd;
+      }
+    }
+  }
+  good = cnt;
+  e2 = err;
+}
+
+__global__ __launch_bounds__(256) void rc_check_kernel(RansacArgs a) {
 #pragma clang fp contract(off)   // every comparison is against rounded fp64 ops, as the host restatement's
   __shared__ int s_list[256];
   __shared__ int s_wtot[4];
@@ -119,7 +173,7 @@ __global__ __launch_bounds__(256) void rc_check_kernel(RcArgs a) {
   bool ok = it < a.iters && n >= k;
   if (ok && edge) {
     int64_t c[RC_MAXN];
-    rc_draws(a, p, it, n, c);
+    ransac_draws(a.seed, p, it, n, k, c);
 #pragma unroll
     for (int j = 0; j < RC_MAXN; ++j)
 #pragma unroll
@@ -133,13 +187,7 @@ __global__ __launch_bounds__(256) void rc_check_kernel(RcArgs a) {
       for (int j = 0; j < RC_MAXN; ++j)
 #pragma unroll
         for (int l = j + 1; l < RC_MAXN; ++l)
-          if (l < k) {
-            const double s0 = s[j][0] - s[l][0], s1 = s[j][1] - s[l][1], s2 = s[j][2] - s[l][2];
-            const double t0 = d[j][0] - d[l][0], t1 = d[j][1] - d[l][1], t2 = d[j][2] - d[l][2];
-            const double ls2 = (s0 * s0 + s1 * s1) + s2 * s2;
-            const double lt2 = (t0 * t0 + t1 * t1) + t2 * t2;
-            if (!(ls2 >= a.sim2 * lt2 && lt2 >= a.sim2 * ls2)) ok = false;
-          }
+          if (l < k && !ransac_edge_ok(s[j], s[l], d[j], d[l], a.sim2)) ok = false;
     }
   }
   bool pass = ok;
@@ -161,7 +209,7 @@ __global__ __launch_bounds__(256) void rc_check_kernel(RcArgs a) {
       const int lt = s_list[tid];
       int64_t c[RC_MAXN];
       double s[RC_MAXN][3], d[RC_MAXN][3], R[3][3], t[3];
-      rc_draws(a, p, blk * 256 + lt, n, c);
+      ransac_draws(a.seed, p, blk * 256 + lt, n, k, c);
       rc_load(x1, c, k, s);
       rc_load(x2, c, k, d);
       rc_fit(s, d, k, R, t);
@@ -169,14 +217,9 @@ __global__ __launch_bounds__(256) void rc_check_kernel(RcArgs a) {
       if (a.cd2 > 0.0) {
 #pragma unroll
         for (int j = 0; j < RC_MAXN; ++j)
+          // (as one condition, `j < k && !(.. < a.cd2)`, the kernel grew from 5,031 to 6,306 instructions)
           if (j < k) {
-            double dd = 0.0;
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-              const double y = ((R[e][0] * s[j][0] + R[e][1] * s[j][1]) + R[e][2] * s[j][2]) + t[e];
-              const double df = y - d[j][e];
-              dd = dd + df * df;
-            }
+            const double dd = ransac_row_d2<3, 1>(&R[0][0], t, s[j], d[j]);
             if (!(dd < a.cd2)) good = false;
           }
       }
@@ -205,7 +248,7 @@ __global__ __launch_bounds__(256) void rc_check_kernel(RcArgs a) {
 }
 
 // the ordered list of the first maxv passing iterations of each pair, and the counts
-__global__ __launch_bounds__(256) void rc_scan_kernel(RcArgs a) {
+__global__ __launch_bounds__(256) void rc_scan_kernel(RansacArgs a) {
   __shared__ int s_sum[256];
   const int p = blockIdx.x, tid = threadIdx.x;
   const uint64_t* bits = a.bits + (int64_t)p * a.nwords;
@@ -239,73 +282,56 @@ __global__ __launch_bounds__(256) void rc_scan_kernel(RcArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void rc_eval_kernel(RcArgs a) {
-#pragma clang fp contract(off)   // as ransac_eval_kernel: the evaluation rounds every op
+// one thread per slot: the hypothesis of its iteration, exported and scored
+template <typename Policy>
+__global__ __launch_bounds__(256) void ransac_eval_kernel(RansacArgs a) {
+#pragma clang fp contract(off)   // the evaluation rounds every op
   __shared__ double tile[RC_TILE][6];
-  const int p = blockIdx.x / a.vpp, blk = blockIdx.x % a.vpp;
-  const int nv = a.n_valid[p];
-  if (blk * 256 >= nv) return;   // uniform: nothing validated here (nv = 0 when n < ransac_n)
+  const int p = Policy::pair(a), blk = Policy::block(a);
   const int n = a.n[p];
+  const int nlive = n >= a.rn ? Policy::live(a, p) : 0;   // no hypotheses below ransac_n (selection: identity)
+  if (blk * 256 >= nlive) return;   // uniform
   const double* x1 = a.x1 + (int64_t)p * a.ps;
   const double* x2 = a.x2 + (int64_t)p * a.ps;
   const int slot = blk * 256 + threadIdx.x;
-  const bool live = slot < nv;
-  const int it = a.valid[(int64_t)p * a.maxv + (live ? slot : 0)];
+  const bool live = slot < nlive;
+  const int it = Policy::iter(a, p, live ? slot : 0);   // a dead lane redoes slot 0's and writes nothing
+  const int64_t at = (int64_t)p * Policy::stride(a) + slot;
   double R[3][3], t[3];
   {
     int64_t c[RC_MAXN];
     double s[RC_MAXN][3], d[RC_MAXN][3];
-    rc_draws(a, p, it, n, c);
+    ransac_draws(a.seed, p, it, n, a.rn, c);
     rc_load(x1, c, a.rn, s);
     rc_load(x2, c, a.rn, d);
     rc_fit(s, d, a.rn, R, t);
   }
   if (live) {
-    double* h = a.hyp + ((int64_t)p * a.maxv + slot) * 12;
+    double* h = a.hyp + at * 12;
     for (int r = 0; r < 3; ++r) {
       for (int c = 0; c < 3; ++c) h[3 * r + c] = R[r][c];
       h[9 + r] = t[r];
     }
   }
-  int good = 0;
-  double e2 = 0.0;
-  for (int b0 = 0; b0 < n; b0 += RC_TILE) {
-    const int nb = min(RC_TILE, n - b0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < nb * 6; i += blockDim.x) {
-      const int r = i / 6, e = i % 6;
-      tile[r][e] = e < 3 ? x1[3 * (int64_t)(b0 + r) + e] : x2[3 * (int64_t)(b0 + r) + e - 3];
-    }
-    __syncthreads();
-    for (int r = 0; r < nb; ++r) {
-      const double* q = tile[r];
-      double dd = 0.0;
-#pragma unroll
-      for (int e = 0; e < 3; ++e) {
-        const double y = ((R[e][0] * q[0] + R[e][1] * q[1]) + R[e][2] * q[2]) + t[e];
-        const double df = y - q[3 + e];
-        dd = dd + df * df;
-      }
-      if (dd < a.d2) {
-        ++good;
-        e2 = e2 + dd;
-      }
-    }
-  }
+  int good;
+  double e2;
+  rc_score(x1, x2, n, R, t, a.d2, tile, good, e2);
   if (live) {
-    a.cnt[(int64_t)p * a.maxv + slot] = good;
-    a.err[(int64_t)p * a.maxv + slot] = e2;
+    a.cnt[at] = good;
+    a.err[at] = e2;
   }
 }
 
-// best validated hypothesis per pair: inliers desc, rmse asc, slot (= iteration) asc
-__global__ __launch_bounds__(256) void rc_select_kernel(RcArgs a, double* T, double* fitness, double* rmse,
-                                                        int32_t* best) {
+// best hypothesis per pair: inliers desc, rmse asc, slot (= iteration) asc (= Open3D's strict-improvement loop)
+template <typename Policy>
+__global__ __launch_bounds__(256) void ransac_select_kernel(RansacArgs a, double* T, double* fitness, double* rmse,
+                                                            int32_t* best) {
   __shared__ int bi[256];
   const int p = blockIdx.x, tid = threadIdx.x;
-  const int n = a.n[p], nv = a.n_valid[p];
-  const int32_t* cnt = a.cnt + (int64_t)p * a.maxv;
-  const double* err = a.err + (int64_t)p * a.maxv;
+  const int n = a.n[p];
+  const int nlive = n >= a.rn ? Policy::live(a, p) : 0;
+  const int32_t* cnt = a.cnt + (int64_t)p * Policy::stride(a);
+  const double* err = a.err + (int64_t)p * Policy::stride(a);
   auto better = [&](int i, int j) {   // slot i strictly before j in the order
     if (j < 0) return i >= 0;
     if (i < 0) return false;
@@ -316,7 +342,7 @@ __global__ __launch_bounds__(256) void rc_select_kernel(RcArgs a, double* T, dou
     return i < j;
   };
   int mine = -1;
-  for (int i = tid; i < nv; i += blockDim.x)
+  for (int i = tid; i < nlive; i += blockDim.x)
     if (cnt[i] > 0 && better(i, mine)) mine = i;
   bi[tid] = mine;
   __syncthreads();
@@ -334,10 +360,11 @@ __global__ __launch_bounds__(256) void rc_select_kernel(RcArgs a, double* T, dou
     rmse[p] = 0.0;
     return;
   }
-  best[p] = a.valid[(int64_t)p * a.maxv + b];
+  best[p] = Policy::iter(a, p, b);
   fitness[p] = (double)cnt[b] / n;
   rmse[p] = sqrt(err[b] / cnt[b]);
-  const double* h = a.hyp + ((int64_t)p * a.maxv + b) * 12;
+  // the winner's transformation: read back from the hypothesis buffer (always allocated by the launchers)
+  const double* h = a.hyp + ((int64_t)p * Policy::stride(a) + b) * 12;
   for (int r = 0; r < 3; ++r) {
     for (int cc = 0; cc < 3; ++cc) Tp[4 * r + cc] = h[3 * r + cc];
     Tp[4 * r + 3] = h[9 + r];
@@ -347,6 +374,39 @@ __global__ __launch_bounds__(256) void rc_select_kernel(RcArgs a, double* T, dou
 static size_t rc_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace mvr
+
+extern "C" size_t mvr_ransac_workspace_bytes(int P, int iters) {
+  if (P <= 0 || iters <= 0) return 0;
+  return (size_t)P * iters * (sizeof(int32_t) + sizeof(double) + 12 * sizeof(double)) + 256;
+}
+
+extern "C" int mvr_ransac(const double* x1, const double* x2, int64_t x_pstride, const int32_t* n, int P, int ransac_n,
+                          int iters, double max_dist, uint64_t seed, double* T, double* fitness, double* rmse,
+                          int32_t* best_iter, double* hyp_out, void* workspace, size_t workspace_bytes,
+                          hipStream_t stream) {
+  if (P < 0 || ransac_n < 3 || ransac_n > mvr::RC_MAXN || iters <= 0 || iters >= (1 << 30) || P >= (1 << 23) ||
+      !(max_dist > 0.0))
+    return MVR_EINVAL;
+  if (P == 0) return MVR_OK;
+  if (!x1 || !x2 || !n || !T || !fitness || !rmse || !best_iter) return MVR_EINVAL;
+  const size_t need = mvr_ransac_workspace_bytes(P, iters) - (hyp_out ? (size_t)P * iters * 12 * sizeof(double) : 0);
+  if (!workspace || workspace_bytes < need) return MVR_EINVAL;
+  mvr::RansacArgs a{};
+  a.x1 = x1; a.x2 = x2; a.ps = x_pstride; a.n = n;
+  a.P = P; a.iters = iters; a.rn = ransac_n; a.d2 = max_dist * max_dist; a.seed = seed;
+  char* w = static_cast<char*>(workspace);
+  a.err = reinterpret_cast<double*>(w);
+  a.cnt = reinterpret_cast<int32_t*>(w + (size_t)P * iters * sizeof(double));
+  a.hyp = hyp_out
+          ? hyp_out
+          : reinterpret_cast<double*>(w + mvr::rc_align((size_t)P * iters * (sizeof(double) + sizeof(int32_t))));
+  hipLaunchKernelGGL(mvr::ransac_eval_kernel<mvr::RansacPlain>, dim3((iters + 255) / 256, P), dim3(256), 0, stream, a);
+  MVR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mvr::ransac_select_kernel<mvr::RansacPlain>, dim3(P), dim3(256), 0, stream, a, T, fitness, rmse,
+                     best_iter);
+  MVR_CHECK_LAUNCH();
+  return MVR_OK;
+}
 
 // per pair: the pass bits, and per validated hypothesis the iteration id, a count, an error sum and 12 doubles
 extern "C" size_t mvr_ransac_checked_workspace_bytes(int P, int iters, int max_validation) {
@@ -373,7 +433,7 @@ extern "C" int mvr_ransac_checked(const double* x1, const double* x2, int64_t x_
   if (!x1 || !x2 || !n || !T || !fitness || !rmse || !best_iter || !n_pass || !n_valid) return MVR_EINVAL;
   if (!workspace || workspace_bytes < mvr_ransac_checked_workspace_bytes(P, iters, max_validation))
     return MVR_EINVAL;
-  mvr::RcArgs a{};
+  mvr::RansacArgs a{};
   a.x1 = x1; a.x2 = x2; a.ps = x_pstride; a.n = n;
   const bool normals = nrm1 && nrm2;
   a.nrm1 = normals ? nrm1 : nullptr; a.nrm2 = normals ? nrm2 : nullptr;
@@ -405,12 +465,13 @@ extern "C" int mvr_ransac_checked(const double* x1, const double* x2, int64_t x_
   MVR_CHECK_LAUNCH();
   {
     mvr::ProfScope prof(mvr::PK_RANSAC_EVAL, 0.0, 0.0, stream);
-    hipLaunchKernelGGL(mvr::rc_eval_kernel, dim3(P * a.vpp), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mvr::ransac_eval_kernel<mvr::RansacListed>, dim3(P * a.vpp), dim3(256), 0, stream, a);
   }
   MVR_CHECK_LAUNCH();
   {
     mvr::ProfScope prof(mvr::PK_RANSAC_SELECT, 0.0, 0.0, stream);
-    hipLaunchKernelGGL(mvr::rc_select_kernel, dim3(P), dim3(256), 0, stream, a, T, fitness, rmse, best_iter);
+    hipLaunchKernelGGL(mvr::ransac_select_kernel<mvr::RansacListed>, dim3(P), dim3(256), 0, stream, a, T, fitness,
+                       rmse, best_iter);
   }
   MVR_CHECK_LAUNCH();
   return MVR_OK;

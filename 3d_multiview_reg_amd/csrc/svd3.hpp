@@ -1,5 +1,5 @@
 // 3 x 3 SVD by one-sided Jacobi in fp64 and the 3 x 3 determinant, shared by the Procrustes / RANSAC kernels
-// (procrustes.hip, ransac_checked.hip), the ICP solve (icp.hip) and the pose synchronisation (sync.hip).
+// (procrustes.hip, ransac.hip), the ICP solve (icp.hip) and the pose synchronisation (sync.hip).
 //
 // H = U diag(S) V^T, S descending, V orthogonal; U's columns of singular values <= 1e-13 S[0] are completed (rank
 // 1: a unit vector orthogonal to u0; rank <= 2: u2 = u0 x u1), so U is orthogonal to rounding at every rank; the

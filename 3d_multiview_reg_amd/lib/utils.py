@@ -358,7 +358,7 @@ RANSAC_N, RANSAC_DIST, RANSAC_ITERS = 4, 0.05, 2500   # utils.py:688,701-705: mi
 
 def run_ransac_batch(xyz_i, xyz_j, counts=None, seed=0, ransac_n=RANSAC_N, max_dist=RANSAC_DIST,
                      iters=RANSAC_ITERS, device=None, return_all=False):
-    """Batched RANSAC over correspondences (csrc/procrustes.hip mvr_ransac): xyz_i, xyz_j [P, n, 3]
+    """Batched RANSAC over correspondences (csrc/ransac.hip mvr_ransac): xyz_i, xyz_j [P, n, 3]
     (torch or numpy; computed in fp64 as Open3D's Vector3d), counts [P] valid rows per pair (default n).
     Returns T [P, 4, 4] float64 numpy (x_j ~ T x_i), and with return_all also fitness, rmse, best_iter."""
     from lib import _native as N
@@ -390,7 +390,7 @@ def run_ransac_batch(xyz_i, xyz_j, counts=None, seed=0, ransac_n=RANSAC_N, max_d
 def run_ransac_checked_batch(xyz_i, xyz_j, counts=None, seed=0, ransac_n=3, max_dist=RANSAC_DIST, iters=100000,
                              max_validation=2500, edge_sim=0.9, check_dist=None, normals_i=None, normals_j=None,
                              normal_deg=None, device=None):
-    """Batched RANSAC with correspondence checkers (csrc/ransac_checked.hip mvr_ransac_checked; the settings of
+    """Batched RANSAC with correspondence checkers (csrc/ransac.hip mvr_ransac_checked; the settings of
     Open3D's global-registration examples): of `iters` samples of ransac_n correspondences, those that pass the
     edge-length checker (edge_sim in [0, 1), 0: off), the distance checker (check_dist, None: max_dist, 0: off)
     and, with normals_i, normals_j [P, n, 3] and normal_deg (the largest angle in degrees between a rotated source

@@ -90,7 +90,7 @@ int mvr_ransac(const double* x1, const double* x2, int64_t x_pstride, const int3
                int32_t* best_iter, double* hyp_out, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * RANSAC with correspondence checkers and a validation cap, batched over pairs (csrc/ransac_checked.hip;
+ * RANSAC with correspondence checkers and a validation cap, batched over pairs (csrc/ransac.hip;
  * DESIGN.md 4.26).  What Open3D's global-registration examples configure (3-point samples,
  * CorrespondenceCheckerBasedOnEdgeLength(0.9) + ...BasedOnDistance, ...BasedOnNormal, 100000 iterations): a cheap
  * test per sample decides whether its hypothesis is scored at all.  It replaces nothing in the reference (whose

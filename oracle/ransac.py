@@ -33,7 +33,7 @@ def splitmix64(z):
 
 
 def draws(seed, p, it, k, n):
-    """indices of draw j < k of iteration `it` of pair p (csrc/procrustes.hip ransac_draw)"""
+    """indices of draw j < k of iteration `it` of pair p (csrc/ransac.hpp ransac_draws)"""
     out = []
     for j in range(k):
         ctr = (p << 40) | (it << 8) | j

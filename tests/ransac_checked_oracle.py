@@ -1,4 +1,4 @@
-"""RANSAC with correspondence checkers restated in numpy (TEST ORACLE for csrc/ransac_checked.hip mvr_ransac_checked;
+"""RANSAC with correspondence checkers restated in numpy (TEST ORACLE for csrc/ransac.hip mvr_ransac_checked;
 the semantics are in include/mvreg.h).  The draws, the Umeyama fit, the evaluation and the selection are
 oracle/ransac.py's (draws and fits vectorised over the iterations here and pinned to O.draws / O.umeyama by
 tests/test_ransac_checked_host.py).

@@ -1,6 +1,7 @@
-"""Batched GPU RANSAC (csrc/procrustes.hip mvr_ransac, lib/utils.py run_ransac[_batch]) against the
+"""Batched GPU RANSAC (csrc/ransac.hip mvr_ransac, lib/utils.py run_ransac[_batch]) against the
 restatement of lib/utils.py:671-709 / Open3D 0.9 in oracle/ransac.py (Open3D itself: parity unpinned):
-  * every hypothesis (same counter-stream draws, Umeyama fit) within 1e-9 of the oracle's numpy-SVD fit, and every
+  * at ransac_n 3, 4, 5 and 8 (the fit is unrolled to 8 sample points and predicated):
+    every hypothesis (same counter-stream draws, Umeyama fit) within 1e-9 of the oracle's numpy-SVD fit, and every
     one, the rank-deficient draws left out of that comparison included, a finite proper rotation to 1e-12;
   * inlier counts / error sums of the GPU's own hypotheses, re-evaluated by the oracle in the kernel's fp64
     operation order: the selected iteration, fitness and rmse identical (bit for bit);
@@ -25,7 +26,7 @@ def _corr(n, inl, seed, noise=0.005):
     return x1, x2, R, t
 
 
-def _gpu(x1, x2, counts, seed, iters, gpu):
+def _gpu(x1, x2, counts, seed, iters, gpu, ransac_n=4):
     import torch
     from lib import _native as N
     P, n = x1.shape[0], x1.shape[1]
@@ -38,26 +39,31 @@ def _gpu(x1, x2, counts, seed, iters, gpu):
     hyp = torch.empty(P, iters, 12, dtype=torch.float64, device=gpu)
     L = N.lib()
     ws = torch.empty(L.mvr_ransac_workspace_bytes(P, iters), dtype=torch.uint8, device=gpu)
-    assert L.mvr_ransac(N.ptr(X1), N.ptr(X2), n * 3, N.ptr(cnt), P, 4, iters, 0.05, seed, N.ptr(T), N.ptr(fit),
+    assert L.mvr_ransac(N.ptr(X1), N.ptr(X2), n * 3, N.ptr(cnt), P, ransac_n, iters, 0.05, seed, N.ptr(T), N.ptr(fit),
                         N.ptr(rmse), N.ptr(best), N.ptr(hyp), N.ptr(ws), ws.numel(), N.stream()) == 0
     torch.cuda.synchronize()
     return T.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy(), best.cpu().numpy(), hyp.cpu().numpy()
 
 
-@pytest.mark.parametrize("n,iters", [(300, 256), (1000, 700), (37, 100)])
-def test_ransac_matches_oracle(gpu, n, iters):
+# ransac_n 3 at (37, 100) is left out: 81-94 % of its iterations draw three distinct rows, under the cap below
+@pytest.mark.parametrize("n,iters,ransac_n", [
+    pytest.param(300, 256, 4, id="300-256"), pytest.param(1000, 700, 4, id="1000-700"),
+    pytest.param(37, 100, 4, id="37-100"), (120, 100, 3), (300, 256, 3), (37, 100, 5), (300, 256, 5), (37, 100, 8),
+    (300, 256, 8)])
+def test_ransac_matches_oracle(gpu, n, iters, ransac_n):
     P = 3
     data = [_corr(n, f, seed=10 + p) for p, f in enumerate((0.05, 0.3, 0.8))]
     x1 = np.stack([d[0] for d in data])
     x2 = np.stack([d[1] for d in data])
     counts = [n, n - 5, n // 2]
-    T, fit, rmse, best, hyp = _gpu(x1, x2, counts, 11, iters, gpu)
+    T, fit, rmse, best, hyp = _gpu(x1, x2, counts, 11, iters, gpu, ransac_n)
     for p in range(P):
         m = counts[p]
-        To, fo, ro, bo, own, _, _ = O.ransac(x1[p, :m], x2[p, :m], seed=11, iters=iters, p=p, hyps=hyp[p])
+        To, fo, ro, bo, own, _, _ = O.ransac(x1[p, :m], x2[p, :m], seed=11, ransac_n=ransac_n, iters=iters, p=p,
+                                             hyps=hyp[p])
         # the fits themselves: GPU Jacobi SVD vs numpy LAPACK on the same draws (draws with fewer than three
         # distinct correspondences have a rank-1 covariance: the rotation is not unique, skip them)
-        ok = [it for it in range(iters) if len(set(O.draws(11, p, it, 4, m))) >= 3]
+        ok = [it for it in range(iters) if len(set(O.draws(11, p, it, ransac_n, m))) >= 3]
         assert len(ok) > 0.9 * iters
         np.testing.assert_allclose(hyp[p][ok], own[ok], atol=1e-9)
         # every hypothesis, the skipped draws included (their covariance has rank 1 or 0: the completion branches
@@ -88,6 +94,19 @@ def test_ragged_and_degenerate(gpu):
         assert np.all(np.isfinite(hyp[p]))
         np.testing.assert_allclose(np.swapaxes(Rh, 1, 2) @ Rh, np.broadcast_to(np.eye(3), Rh.shape), rtol=0, atol=1e-12)
         np.testing.assert_allclose(np.linalg.det(Rh), 1.0, rtol=0, atol=1e-12)
+    # ransac_n = 8: a pair one below the sample size and one exactly at it
+    T, fit, rmse, best, hyp = _gpu(x1, x2, [0, 7, 8, 64], 5, 64, gpu, ransac_n=8)
+    for p in (0, 1):
+        assert best[p] == -1 and fit[p] == 0.0 and rmse[p] == 0.0 and np.array_equal(T[p], np.eye(4))
+    assert best[2] >= 0 and fit[2] > 0 and best[3] >= 0
+    for p in (2, 3):
+        Rh = hyp[p][:, :9].reshape(64, 3, 3)
+        assert np.all(np.isfinite(hyp[p]))
+        np.testing.assert_allclose(np.swapaxes(Rh, 1, 2) @ Rh, np.broadcast_to(np.eye(3), Rh.shape), rtol=0, atol=1e-12)
+        np.testing.assert_allclose(np.linalg.det(Rh), 1.0, rtol=0, atol=1e-12)
+        m = [0, 7, 8, 64][p]
+        To, fo, ro, bo = O.ransac(x1[p, :m], x2[p, :m], seed=5, ransac_n=8, iters=64, p=p, hyps=hyp[p])[:4]
+        assert best[p] == bo and fit[p] == fo and rmse[p] == ro and np.array_equal(T[p], To)
 
 
 def test_batch_equals_single_calls(gpu):

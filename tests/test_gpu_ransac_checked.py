@@ -1,4 +1,4 @@
-"""GPU RANSAC with correspondence checkers (csrc/ransac_checked.hip mvr_ransac_checked,
+"""GPU RANSAC with correspondence checkers (csrc/ransac.hip mvr_ransac_checked,
 lib.utils.run_ransac_checked_batch, register_fpfh(checkers=...), register_scene(ransac_checkers=...)) against
 mvr_ransac (checkers off: byte-identical) and the numpy restatement tests/ransac_checked_oracle.py:
   * the pass bits equal the oracle's on every iteration the oracle calls decided (no comparison within 1e-9 / 1e-7 of

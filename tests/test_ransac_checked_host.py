@@ -1,4 +1,4 @@
-"""CPU checks of the checked RANSAC (csrc/ransac_checked.hip mvr_ransac_checked): the numpy restatement
+"""CPU checks of the checked RANSAC (csrc/ransac.hip mvr_ransac_checked): the numpy restatement
 (tests/ransac_checked_oracle.py) against oracle/ransac.py and against hand-worked cases, the share of undecided
 iterations on every input tests/test_gpu_ransac_checked.py runs, the quality case the feature exists for, and the
 parts of the ABI and of the Python wrappers that return before any GPU call."""

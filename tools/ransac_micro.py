@@ -1,7 +1,7 @@
-"""Timing of the batched GPU RANSAC (csrc/procrustes.hip mvr_ransac) at the benchmark's --refine / RANSAC
+"""Timing of the batched GPU RANSAC (csrc/ransac.hip mvr_ransac) at the benchmark's --refine / RANSAC
 baseline shape: P pairs x 5000 correspondences x 2500 iterations (lib/utils.py:671-709), HIP events, plus
 the numpy restatement (oracle/ransac.py) on one pair with fewer iterations, scaled.
---checked: right after it, on the same inputs and in the same process, mvr_ransac_checked (csrc/ransac_checked.hip) at
+--checked: right after it, on the same inputs and in the same process, mvr_ransac_checked (csrc/ransac.hip) at
 its defaults (3-point samples, 100000 draws, at most 2500 scored, edge 0.9, distance 0.05) beside mvr_ransac: HIP
 events per call after a warm-up, median / min / max over --reps, the ratio, and the split over its four kernels (the
 library's own event pairs around each launch, one more run).
