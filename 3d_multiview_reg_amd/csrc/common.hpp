@@ -53,6 +53,24 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* red) {
   __syncthreads();
 }
 
+// Block-wide maximum of a double; result valid in every thread.  `red` must hold blockDim/64 doubles of LDS.  Seeded
+// from the first wave's value: the callers (fgr.hip, posegraph.hip) pass 0 / 1 flags or values built by fmax from 0.0,
+// never NaN and never negative, so a seed of 0.0 would give the same bits.  kWaves: the waves of the block where the
+// caller knows them at compile time (posegraph_kernel<false> spills one register more with the count read from
+// blockDim); 0: from blockDim.
+template <int kWaves = 0>
+__device__ __forceinline__ double block_max(double v, double* red) {
+  const int w = threadIdx.x >> 6, nw = kWaves ? kWaves : (int)(blockDim.x >> 6), l = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  if (l == 0) red[w] = v;
+  __syncthreads();
+  double m = red[0];
+  for (int j = 1; j < nw; ++j) m = fmax(m, red[j]);
+  __syncthreads();
+  return m;
+}
+
 // LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4): lane l's bytes from base + off land at LDS byte address
 // lds + 16 l.  base and lds wave-uniform (SGPRs), off a 32-bit lane offset: no 64-bit per-lane pointers or
 // generic-to-LDS casts stay live in a loop.  Inline asm: the compiler does not count it, so the caller waits

@@ -8,7 +8,7 @@
 //
 // One workgroup per pair, every phase and every iteration inside the one launch (as icp_core.hpp's icp_loop), nothing
 // atomic, every sum through block_sum in its fixed order: the result is a function of (inputs, seed) alone.
-//   1. all n rows: finiteness, the means mu1, mu2 and scale = max |x - mu| (block_sum, a block maximum);
+//   1. all n rows: finiteness, the means mu1, mu2 and scale = max |x - mu| (common.hpp's block_sum and block_max);
 //   2. the used rows, normalised ((x - mu) / scale), into the pair's slab of the workspace: with the tuple filter the
 //      tests are walked in chunks of one test per thread in ascending order, the passing ones appended in order
 //      (a 64-bit ballot per wave, per-wave counts through LDS) until max_tuples is reached or the tests are exhausted;
@@ -43,19 +43,6 @@ struct FgrArgs {
   double* T; double* fitness; double* rmse; int32_t* n_used; int32_t* n_tuples; int32_t* status; double* trace;
   double* pts;                       // [P][cap][6]: the used rows, normalised (p, q)
 };
-
-// red: one double per wave
-__device__ __forceinline__ double block_max(double v, double* red) {
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6, l = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  if (l == 0) red[w] = v;
-  __syncthreads();
-  double m = red[0];
-  for (int j = 1; j < nw; ++j) m = fmax(m, red[j]);
-  __syncthreads();
-  return m;
-}
 
 template <int kThreads>
 __device__ __forceinline__ void fgr_pair(const FgrArgs& a) {

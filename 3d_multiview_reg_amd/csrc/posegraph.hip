@@ -21,9 +21,9 @@
 //   trial    candidate poses from delta, their cost by a block sum over the edges, accept or reject
 // The matrix lives in the workspace (6N x 6N doubles: 1 MB at 60 fragments, 4.7 MB at 128; L2-resident); LDS holds the
 // poses, the candidate, delta and the panel.  Every loop is bounded: max_iters, N factor steps, N solve steps.
-#include "common.hpp"
-#include "mvreg.h"
-#include <math.h>
+// Which edges count, the anchor's component and the entries' shared argument rules are scene.hpp's, as sync.hip's
+// (DESIGN.md 4.31); the information matrix's test rides in the edge test as its per-edge rule.
+#include "scene.hpp"
 #include <type_traits>
 
 namespace mvr {
@@ -99,19 +99,6 @@ __device__ static double pg_quad(const double* L, const double* xi) {
     acc += xi[r] * row;
   }
   return acc;
-}
-
-// block-wide maximum of a non-negative value, valid in every thread
-__device__ static double block_max(double v, double* red) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  if (l == 0) red[w] = v;
-  __syncthreads();
-  double m = 0.0;
-  for (int j = 0; j < kPgThreads / 64; ++j) m = fmax(m, red[j]);
-  __syncthreads();
-  return m;
 }
 
 // the lower Cholesky factor of the 6 x 6 block at A (leading dimension n), read through loads every thread shares;
@@ -212,56 +199,27 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(
   const int n = 6 * N;
   __syncthreads();   // sFlag[0] read by everyone before it is reused
 
-  // ---- the edges that count, the members (as sync.hip)
+  // ---- the edges that count, the members (scene.hpp); the edge's own rule: info finite, symmetric to 1e-9 |L|_F
   for (int f = tid; f < N; f += kPgThreads) {
     sMem[f] = (f == anchor);
     for (int q = 0; q < 9; ++q) sR[f][q] = R0[9 * f + q];
     for (int q = 0; q < 3; ++q) sT[f][q] = t0[3 * f + q];
   }
   __syncthreads();
-  {
-    int ign = 0;
-    for (int e = tid; e < E; e += kPgThreads) {
-      const int i = ij[2 * e], j = ij[2 * e + 1];
-      const double wgt = win ? win[e] : 1.0;
-      bool ok = i >= 0 && i < N && j >= 0 && j < N && i != j && isfinite(wgt) && wgt >= 0.0;
-      for (int q = 0; q < 9; ++q) ok = ok && isfinite(Rp[(int64_t)9 * e + q]);
-      for (int q = 0; q < 3; ++q) ok = ok && isfinite(tp[(int64_t)3 * e + q]);
-      const double* Le = info + (int64_t)36 * e;
-      double fro = 0.0, asym = 0.0;
-      for (int q = 0; q < 36; ++q) {
-        ok = ok && isfinite(Le[q]);
-        fro += Le[q] * Le[q];
-        asym = fmax(asym, fabs(Le[q] - Le[6 * (q % 6) + q / 6]));
-      }
-      ok = ok && !(asym > 1e-9 * sqrt(fro));
-      wc[e] = ok ? wgt : -1.0;
-      ign |= !ok;
+  scene_edge_test<kPgThreads>(Rp, tp, ij, win, N, E, wc, sFlag, [&](int e) {
+    const double* Le = info + (int64_t)36 * e;
+    bool ok = true;
+    double fro = 0.0, asym = 0.0;
+    for (int q = 0; q < 36; ++q) {
+      ok = ok && isfinite(Le[q]);
+      fro += Le[q] * Le[q];
+      asym = fmax(asym, fabs(Le[q] - Le[6 * (q % 6) + q / 6]));
     }
-    if (ign) atomicOr(&sFlag[0], 4);
-  }
-  __syncthreads();
-  for (int round = 0; round <= N; ++round) {
-    if (tid == 0) sFlag[1] = 0;
-    __syncthreads();
-    for (int e = tid; e < E; e += kPgThreads)
-      if (wc[e] > 0.0) {
-        const int i = ij[2 * e], j = ij[2 * e + 1];
-        if (sMem[i] != sMem[j]) { sMem[i] = 1; sMem[j] = 1; sFlag[1] = 1; }
-      }
-    __syncthreads();
-    const int changed = sFlag[1];
-    __syncthreads();
-    if (!changed) break;
-  }
-  int Nm = 0;
-  for (int f = 0; f < N; ++f) Nm += sMem[f];
+    return ok && !(asym > 1e-9 * sqrt(fro));
+  });
+  const int Nm = scene_component<kPgThreads>(ij, N, E, wc, sMem, sFlag);
   int status = sFlag[0] | (Nm < N ? 1 : 0);
-  for (int e = tid; e < E; e += kPgThreads) {
-    double wgt = fmax(wc[e], 0.0);
-    if (wgt > 0.0 && !sMem[ij[2 * e]]) wgt = 0.0;
-    wc[e] = wgt;
-  }
+  for (int e = tid; e < E; e += kPgThreads) wc[e] = fmax(wc[e], 0.0);   // in place: 0 for an ignored edge
   __syncthreads();
 
   // c = sum_k w_k xi_k^T L_k xi_k at the poses (PR, PT), in every thread
@@ -523,7 +481,7 @@ __global__ __launch_bounds__(kPgThreads) void posegraph_kernel(
         }
         for (int q = 0; q < 6; ++q) mx = fmax(mx, fabs(d[q]));
       }
-      step = block_max(mx, red);   // its barriers also order the candidate's writes before the reads below
+      step = block_max<kPgThreads / 64>(mx, red);   // its barriers order the candidate's writes before the reads below
       double sums[2];
       if constexpr (kLineProcess) {
         cost_lp(cR, cT, sums);
@@ -600,15 +558,13 @@ static int pg_arguments(const double* R_pair, const double* t_pair, const int32_
                         int32_t* member, double* cost, int32_t* iters, int32_t* status, double* trace, void* workspace,
                         size_t workspace_bytes, size_t need, int64_t extra, mvr::PgArgs& a, bool* launch) {
   *launch = false;
-  if (S < 0 || max_frags < 0 || max_edges < 0 || max_iters < 0 || max_frags > MVR_SYNC_MAX_FRAGS || anchor < 0 ||
-      (max_frags > 0 && anchor >= max_frags))
-    return MVR_EINVAL;
+  if (!mvr::scene_counts_ok(S, max_frags, max_edges, anchor) || max_iters < 0) return MVR_EINVAL;
   if (!(lambda0 >= 0.0) || !isfinite(lambda0) || !(tol_cost >= 0.0) || !(tol_step >= 0.0)) return MVR_EINVAL;
   if (S == 0 || max_frags == 0) return MVR_OK;   // nothing to write: NULL pointers allowed
   if (!n_edges || !n_frags || !status || !cost || !iters || !R || !t || !R0 || !t0) return MVR_EINVAL;
   if (max_edges > 0 && (!R_pair || !t_pair || !ij || !info)) return MVR_EINVAL;
-  if (S > 1 && (e_sstride < max_edges || f_sstride < max_frags)) return MVR_EINVAL;
-  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7)) return MVR_EINVAL;
+  if (!mvr::scene_buffers_ok(S, max_frags, max_edges, e_sstride, f_sstride, workspace, workspace_bytes, need))
+    return MVR_EINVAL;
   a.Rp = R_pair; a.tp = t_pair; a.ij = ij; a.w = w; a.info = info; a.es = e_sstride;
   a.n_edges = n_edges; a.n_frags = n_frags;
   a.max_frags = max_frags; a.max_edges = max_edges; a.anchor = anchor;

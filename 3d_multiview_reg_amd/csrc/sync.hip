@@ -16,10 +16,10 @@
 //   weigh    per-edge residuals and the next pass's weights
 // The matrix lives in LDS up to kSyncLdsFrags fragments (3N <= 126: 124 KiB) and in the workspace (L2) above that;
 // the code is the same, the launcher picks the instantiation from max_frags.
-#include "common.hpp"
+// Which edges count, the anchor's component and the entry's shared argument rules are scene.hpp's, as posegraph.hip's
+// (DESIGN.md 4.31); w0 (the base weight of every IRLS pass) and w (the pass's) stay apart here.
+#include "scene.hpp"
 #include "svd3.hpp"
-#include "mvreg.h"
-#include <math.h>
 
 namespace mvr {
 
@@ -183,51 +183,20 @@ __global__ __launch_bounds__(kSyncThreads) void sync_kernel(SyncArgs a) {
   }
   const int n = 3 * N;
 
-  // ---- the edges that count: w0 = the weight, -1 for an ignored edge
+  // ---- the edges that count (scene.hpp): w0 = the weight, -1 for an ignored edge
   if (tid == 0) sFlag[0] = 0;
   for (int f = tid; f < N; f += kSyncThreads) sMem[f] = (f == anchor);
   __syncthreads();
-  {
-    int ign = 0;
-    for (int e = tid; e < E; e += kSyncThreads) {
-      const int i = ij[2 * e], j = ij[2 * e + 1];
-      const double wv = win ? win[e] : 1.0;
-      bool ok = i >= 0 && i < N && j >= 0 && j < N && i != j && isfinite(wv) && wv >= 0.0;
-      for (int q = 0; q < 9; ++q) ok = ok && isfinite(Rp[(int64_t)9 * e + q]);
-      for (int q = 0; q < 3; ++q) ok = ok && isfinite(tp[(int64_t)3 * e + q]);
-      w0[e] = ok ? wv : -1.0;
-      ign |= !ok;
-    }
-    if (ign) atomicOr(&sFlag[0], 4);
-  }
-  __syncthreads();
+  scene_edge_test<kSyncThreads>(Rp, tp, ij, win, N, E, w0, sFlag, [](int) { return true; });
   if (N == 1) {   // uniform
     identity_scene(1, E, 1, sFlag[0]);
     return;
   }
 
-  // ---- members: the anchor's component over the edges with w0 > 0
-  for (int round = 0; round <= N; ++round) {
-    if (tid == 0) sFlag[1] = 0;
-    __syncthreads();
-    for (int e = tid; e < E; e += kSyncThreads)
-      if (w0[e] > 0.0) {
-        const int i = ij[2 * e], j = ij[2 * e + 1];
-        if (sMem[i] != sMem[j]) { sMem[i] = 1; sMem[j] = 1; sFlag[1] = 1; }
-      }
-    __syncthreads();
-    const int changed = sFlag[1];
-    __syncthreads();
-    if (!changed) break;
-  }
-  int Nm = 0;
-  for (int f = 0; f < N; ++f) Nm += sMem[f];
+  // ---- members: the anchor's component.  w0 stays the base of every IRLS pass, wc is the pass's weight
+  const int Nm = scene_component<kSyncThreads>(ij, N, E, w0, sMem, sFlag);
   int status = sFlag[0] | (Nm < N ? 1 : 0);
-  for (int e = tid; e < E; e += kSyncThreads) {
-    double wv = w0[e];
-    if (wv > 0.0 && !sMem[ij[2 * e]]) { wv = 0.0; w0[e] = 0.0; }
-    wc[e] = fmax(wv, 0.0);
-  }
+  for (int e = tid; e < E; e += kSyncThreads) wc[e] = fmax(w0[e], 0.0);
   __syncthreads();
 
   // stage edges [c0, c0 + cnt) for the builders: endpoints (-1: contributes nothing), weights, R_k and t_k
@@ -511,17 +480,14 @@ extern "C" int mvr_sync_poses(const double* R_pair, const double* t_pair, const 
                               double* t, int64_t f_sstride, int32_t* member, double* w_out, double* res_rot,
                               double* res_trans, int32_t* status, void* workspace, size_t workspace_bytes,
                               hipStream_t stream) {
-  if (S < 0 || max_frags < 0 || max_edges < 0 || irls_iters < 0 || max_frags > MVR_SYNC_MAX_FRAGS || anchor < 0 ||
-      (max_frags > 0 && anchor >= max_frags))
-    return MVR_EINVAL;
+  if (!mvr::scene_counts_ok(S, max_frags, max_edges, anchor) || irls_iters < 0) return MVR_EINVAL;
   if (irls_iters > 0 && !(c_rot > 0.0 && c_trans > 0.0)) return MVR_EINVAL;
   if (S == 0) return MVR_OK;
   if (!n_edges || !n_frags || !status) return MVR_EINVAL;
   if (max_frags > 0 && (!R || !t)) return MVR_EINVAL;
   if (max_edges > 0 && (!R_pair || !t_pair || !ij)) return MVR_EINVAL;
-  if (S > 1 && (e_sstride < max_edges || f_sstride < max_frags)) return MVR_EINVAL;
-  if (!workspace || workspace_bytes < mvr_sync_workspace_bytes(S, max_frags, max_edges) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 7))
+  if (!mvr::scene_buffers_ok(S, max_frags, max_edges, e_sstride, f_sstride, workspace, workspace_bytes,
+                             mvr_sync_workspace_bytes(S, max_frags, max_edges)))
     return MVR_EINVAL;
   mvr::SyncArgs a{};
   a.Rp = R_pair; a.tp = t_pair; a.ij = ij; a.w = w; a.es = e_sstride;

@@ -245,6 +245,18 @@ def check(rc, name):
         raise RuntimeError("%s failed with code %d" % (name, rc))
 
 
+def hand_back(out, like, unbatch=False):
+    """A dict of device tensors as the caller gets it: on the device when the argument `like` was there, otherwise on
+    the host, as numpy when `like` was no tensor.  unbatch: without the leading [1] a single scene was given."""
+    if unbatch:
+        out = {k: v[0] for k, v in out.items()}
+    if not (torch.is_tensor(like) and like.device.type == "cuda"):
+        out = {k: v.cpu() for k, v in out.items()}
+        if not torch.is_tensor(like):
+            out = {k: v.numpy() for k, v in out.items()}
+    return out
+
+
 def source_hash():
     """The loaded library's source identity (csrc/Makefile SRC_HASH; variant builds append their flags)."""
     buf = ctypes.create_string_buffer(128)

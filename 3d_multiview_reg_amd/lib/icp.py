@@ -72,7 +72,6 @@ def _run(name, fo, pairs, T_in, T_name, max_dist, needs_normals, call, normals_f
     if max_dist > fo.r:
         raise ValueError("%s: max_dist %g exceeds the index's cell size %g (build the FragmentOverlap with "
                          "radius >= max_dist)" % (name, max_dist, fo.r))
-    was_numpy = not torch.is_tensor(T_in)
     Tin = torch.as_tensor(T_in)
     if Tin.dim() != 3 or tuple(Tin.shape[1:]) not in ((4, 4), (3, 4)) or not Tin.is_floating_point():
         raise ValueError("%s: %s must be a float [P,4,4] or [P,3,4]" % (name, T_name))
@@ -88,13 +87,8 @@ def _run(name, fo, pairs, T_in, T_name, max_dist, needs_normals, call, normals_f
             raise ValueError("%s: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
                              % (name, fo.M))
     N.require_hip()
-    out = call(int(Tin.shape[0]), ij.to(fo.device, torch.int64).contiguous(),
-               Tin[:, :3, :].to(fo.device, torch.float64).contiguous())
-    if Tin.device.type != "cuda":
-        out = {k: v.cpu() for k, v in out.items()}
-        if was_numpy:
-            out = {k: v.numpy() for k, v in out.items()}
-    return out
+    return N.hand_back(call(int(Tin.shape[0]), ij.to(fo.device, torch.int64).contiguous(),
+                            Tin[:, :3, :].to(fo.device, torch.float64).contiguous()), T_in)
 
 
 def _refine(name, fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace, entry, needs_normals,

@@ -4,13 +4,17 @@
 an eigenproblem for the rotations, a linear solve for the translations) with optional IRLS, on the GPU
 (csrc/sync.hip mvr_sync_poses; the maths and the conventions are in DESIGN.md 4.18).  The
 reference never released this stage, so there is no reference module behind this file.
-`optimize_pose_graph` refines those poses over SE(3) (csrc/posegraph.hip), `fuse_scene` maps the fragments
-by them and merges the points per voxel into the registered scene (csrc/fuse.hip mvr_fuse_scene), and
-`register_scene` composes the library's stages from fragments to that scene without a pretrained network.
+`optimize_pose_graph` refines those poses over SE(3) (csrc/posegraph.hip); both take a batch of scenes
+through one marshaller, `_scene_batch`, as their kernels share csrc/scene.hpp.  `fuse_scene` maps the
+fragments by the poses and merges the points per voxel into the registered scene (csrc/fuse.hip mvr_fuse_scene,
+DESIGN.md 4.25), and `register_scene` composes the library's stages from fragments to that scene without a pretrained
+network.
 
 Conventions: edge k = (i, j) with x_j ~ R_k x_i + t_k (source i, target j: lib.utils.pair_index order, the rot_est /
 trans_est of filter_correspondences); pose (R_i, t_i) maps fragment i into the anchor's frame, X = R_i x_i + t_i.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -24,6 +28,118 @@ def _as_list(x):
     return list(x) if isinstance(x, (list, tuple)) else None
 
 
+FLAG = "flag"   # a field's dtype: anything comparable with 0, kept as int32 (non-zero -> 1)
+
+
+def _field(x, dtype, dev):
+    x = torch.as_tensor(x)
+    return (x.to(dev) != 0).to(torch.int32) if dtype == FLAG else x.to(dev, dtype)
+
+
+def _scene_batch(name, edge_fields, frag_fields, n_frags, n_edges, anchor, like):
+    """The marshalling `synchronize` and `optimize_pose_graph` share: a batch of scenes, each an edge list over its
+    fragments, in one of three forms -> padded contiguous tensors.
+
+    edge_fields / frag_fields: (label, value, trailing shape, dtype, optional) per array with one row per edge / per
+    fragment; the first of each gives the count (frag_fields may be empty: n_frags then gives the fragments).  dtype
+    torch.float64, torch.int32 or FLAG; an optional field may be None and stays None.  The forms: one scene (values
+    [E, ...]), per-scene lists of such, or a padded batch ([S, E, ...]) with n_frags / n_edges [S] (defaults: all).
+    like: the argument that decides the placement: the tensors go to its device when it is on one (else to the
+    current HIP device, or stay on the host when there is none: the rules can be checked without a device) and
+    finish() hands the outputs back where it was (N.hand_back).
+    Every broken rule is a ValueError.  Returns a namespace of x (label -> [S, count, ...] or None), S, Fmax, Emax, the
+    host lists nf, ne, their int32 device copies n_f, n_e, dev, and finish(dict of [S, ...] tensors)."""
+    lists = _as_list(like)
+    first = like if lists is None else (like[0] if lists else torch.zeros(0))
+    if torch.is_tensor(first) and first.device.type == "cuda":
+        dev = first.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    groups = (("pose", "F", frag_fields), ("edge", "E", edge_fields))
+    for _, _, fields in groups:
+        for label, value, _, _, optional in fields:
+            if value is None and not optional:
+                raise ValueError("%s: %s is required" % (name, label))
+    x, counts, sizes = {}, {}, {}
+    if lists is not None:   # per-scene lists -> padded
+        S = len(lists)
+        if any(_as_list(v) is None or len(v) != S for _, _, fs in groups for _, v, _, _, _ in fs if v is not None):
+            raise ValueError("%s: the per-scene lists must have one entry per scene" % name)
+        for what, _, fields in groups:
+            for label, value, tail, dtype, _ in fields:
+                if value is None:
+                    x[label] = None
+                    continue
+                per, rows = int(np.prod(tail, dtype=np.int64)), []
+                for s in range(S):
+                    v = _field(value[s], dtype, dev)
+                    if v.numel() % per or (what in counts and v.numel() // per != counts[what][s]):
+                        raise ValueError("%s: scene %d: one %s per %s" % (name, s, label, what))
+                    rows.append(v.reshape((v.numel() // per,) + tail))
+                counts.setdefault(what, [int(r.shape[0]) for r in rows])
+                sizes[what] = max(counts[what] + [0])
+                x[label] = torch.zeros((S, sizes[what]) + tail, dtype=torch.int32 if dtype == FLAG else dtype,
+                                       device=dev)
+                for s in range(S):
+                    x[label][s, :counts[what][s]] = rows[s]
+    else:
+        S = batched = None
+        for what, sym, fields in groups:
+            for k, (label, value, tail, dtype, _) in enumerate(fields):
+                if value is None:
+                    x[label] = None
+                    continue
+                v = _field(value, dtype, dev)
+                if k == 0:   # the field that gives the count
+                    if v.dim() < len(tail) + 1 or tuple(v.shape[v.dim() - len(tail):]) != tail or \
+                            v.dim() - len(tail) not in ((1, 2) if batched is None else (2 if batched else 1,)):
+                        shape = ",".join([sym] + [str(d) for d in tail])
+                        raise ValueError("%s: %s must be [%s] or [S,%s]%s" % (
+                            name, label, shape, shape, "" if batched is None else ", as %s is" % like_label))
+                    if batched is None:
+                        batched, like_label = v.dim() - len(tail) == 2, label
+                    v = v if batched else v.unsqueeze(0)
+                    if S is not None and v.shape[0] != S:
+                        raise ValueError("%s: %s and %s must hold the same scenes" % (name, like_label, label))
+                    S, sizes[what] = int(v.shape[0]), int(v.shape[1])
+                else:
+                    try:
+                        v = v.reshape((S, sizes[what]) + tail)
+                    except RuntimeError:
+                        raise ValueError("%s: %s must be given one %sper %s"
+                                         % (name, label, "row " if what == "pose" else "", what)) from None
+                x[label] = v.contiguous()
+
+        def given(n, most, what, sym):
+            c = [most] * S if n is None else [int(v) for v in torch.as_tensor(n).reshape(-1).tolist()]
+            if len(c) != S or min(c + [0]) < 0 or max(c + [0]) > most:
+                raise ValueError("%s: %s must be [S] with 0 <= %s <= %s" % (name, what, what, sym))
+            return c
+        counts["edge"] = given(n_edges, sizes["edge"], "n_edges", "E")
+        if frag_fields:
+            counts["pose"] = given(n_frags, sizes["pose"], "n_frags", "F")
+    if not frag_fields:   # the fragments are counted, not given
+        counts["pose"] = [int(v) for v in torch.as_tensor(n_frags).reshape(-1).tolist()]
+        if len(counts["pose"]) != S or min(counts["pose"] + [0]) < 0:
+            raise ValueError("%s: n_frags must give one count per scene, none negative" % name)
+        sizes["pose"] = max(counts["pose"] + [0])
+    if sizes["pose"] > MAX_FRAGS:
+        raise ValueError("%s: at most %d fragments per scene" % (name, MAX_FRAGS))
+    if not 0 <= int(anchor) < max(sizes["pose"], 1):
+        raise ValueError("%s: anchor outside the fragments" % name)
+    single = lists is None and not batched
+    return SimpleNamespace(x=x, S=S, Fmax=sizes["pose"], Emax=sizes["edge"], nf=counts["pose"], ne=counts["edge"],
+                           n_f=torch.tensor(counts["pose"], dtype=torch.int32).to(dev),
+                           n_e=torch.tensor(counts["edge"], dtype=torch.int32).to(dev), dev=dev,
+                           finish=lambda out: N.hand_back(out, first, single))
+
+
+def _edge_fields(R_pair, t_pair, pairs, weights):
+    """_scene_batch's per-edge fields of both entries"""
+    return (("R_pair", R_pair, (3, 3), torch.float64, False), ("t_pair", t_pair, (3,), torch.float64, False),
+            ("pair", pairs, (2,), torch.int32, False), ("weight", weights, (), torch.float64, True))
+
+
 def synchronize(R_pair, t_pair, pairs, n_frags, weights=None, anchor=0, irls_iters=0, c_rot=0.1, c_trans=0.1,
                 n_edges=None):
     """Poses of every fragment from pairwise estimates (batched over scenes, one launch).
@@ -31,89 +147,32 @@ def synchronize(R_pair, t_pair, pairs, n_frags, weights=None, anchor=0, irls_ite
     One scene: R_pair [E,3,3], t_pair [E,3] (or [E,3,1]), pairs [E,2], n_frags int, weights [E] or None (all ones).
     A batch: lists of such per-scene arrays with n_frags a list, or padded R_pair [S,E,3,3], t_pair [S,E,3],
     pairs [S,E,2], weights [S,E] with n_frags [S] and n_edges [S] (default E for every scene).
-    Inputs are torch tensors or numpy arrays, fp32 or fp64; the solve is fp64.
+    Inputs are torch tensors or numpy arrays, fp32 or fp64; the solve is fp64.  A shape or a count that breaks these
+    rules is a ValueError, raised before a device is asked for.
     Returns a dict of fp64 R [N,3,3], t [N,3], int32 member [N], fp64 weights / res_rot / res_trans [E] (the last
     IRLS pass's weights and per-edge residuals) and int32 status (bits: 1 some fragment is not connected to the
     anchor and came out as identity with member 0, 2 an eigen-solve hit its iteration cap, 4 an edge was ignored or
     the scene is invalid); a batch adds a leading [S] (padded to the largest N and E).  The outputs stay on the
     device when R_pair was on the device; otherwise they come back on the host (numpy for numpy inputs)."""
+    b = _scene_batch("synchronize", _edge_fields(R_pair, t_pair, pairs, weights), (), n_frags, n_edges, anchor, R_pair)
     N.require_hip()
-    was_numpy = not torch.is_tensor(R_pair if _as_list(R_pair) is None else R_pair[0])
-    first = torch.as_tensor(R_pair if _as_list(R_pair) is None else R_pair[0])
-    on_dev = first.device.type == "cuda"
-    dev = first.device if on_dev else torch.device("cuda", torch.cuda.current_device())
-
-    def f64(x, tail):
-        return torch.as_tensor(x).to(dev, torch.float64).reshape((-1,) + tail)
-
-    lists = _as_list(R_pair)
-    if lists is not None:   # per-scene lists -> padded
-        S = len(lists)
-        nf = [int(v) for v in n_frags]
-        if not (len(t_pair) == len(pairs) == len(nf) == S) or (weights is not None and len(weights) != S):
-            raise ValueError("synchronize: the per-scene lists must have one entry per scene")
-        Rs = [f64(x, (3, 3)) for x in R_pair]
-        ne = [int(x.shape[0]) for x in Rs]
-        Emax = max(ne) if ne else 0
-        Rp = torch.zeros(S, Emax, 3, 3, dtype=torch.float64, device=dev)
-        tp = torch.zeros(S, Emax, 3, dtype=torch.float64, device=dev)
-        ij = torch.zeros(S, Emax, 2, dtype=torch.int32, device=dev)
-        w = None if weights is None else torch.zeros(S, Emax, dtype=torch.float64, device=dev)
-        for s in range(S):
-            Rp[s, :ne[s]] = Rs[s]
-            tp[s, :ne[s]] = f64(t_pair[s], (3,))
-            ij[s, :ne[s]] = torch.as_tensor(pairs[s]).to(dev, torch.int32).reshape(-1, 2)
-            if w is not None:
-                w[s, :ne[s]] = f64(weights[s], ())
-        batched = True
-    else:
-        Rp = torch.as_tensor(R_pair).to(dev, torch.float64)
-        batched = Rp.dim() == 4
-        if Rp.dim() not in (3, 4) or tuple(Rp.shape[-2:]) != (3, 3):
-            raise ValueError("synchronize: R_pair must be [E,3,3] or [S,E,3,3]")
-        if not batched:
-            Rp = Rp.unsqueeze(0)
-        S, Emax = Rp.shape[0], Rp.shape[1]
-        Rp = Rp.contiguous()
-        tp = torch.as_tensor(t_pair).to(dev, torch.float64).reshape(S, Emax, 3).contiguous()
-        ij = torch.as_tensor(pairs).to(dev, torch.int32).reshape(S, Emax, 2).contiguous()
-        w = None if weights is None else torch.as_tensor(weights).to(dev, torch.float64).reshape(S, Emax).contiguous()
-        nf = [int(v) for v in torch.as_tensor(n_frags).reshape(-1).tolist()]
-        if len(nf) != S:
-            raise ValueError("synchronize: n_frags must give one count per scene")
-        ne = [Emax] * S if n_edges is None else [int(v) for v in torch.as_tensor(n_edges).reshape(-1).tolist()]
-        if len(ne) != S or min(ne + [0]) < 0 or max(ne + [0]) > Emax:
-            raise ValueError("synchronize: n_edges must be [S] with 0 <= n_edges <= E")
-    Fmax = max(nf + [0])
-    if min(nf + [0]) < 0 or Fmax > MAX_FRAGS:
-        raise ValueError("synchronize: n_frags must be within [0, %d]" % MAX_FRAGS)
-    if not 0 <= int(anchor) < max(Fmax, 1):
-        raise ValueError("synchronize: anchor outside the fragments")
-    n_e = torch.tensor(ne, dtype=torch.int32).to(dev)
-    n_f = torch.tensor(nf, dtype=torch.int32).to(dev)
-    R = torch.empty(S, Fmax, 3, 3, dtype=torch.float64, device=dev)
-    t = torch.empty(S, Fmax, 3, dtype=torch.float64, device=dev)
+    S, Fmax, Emax, dev = b.S, b.Fmax, b.Emax, b.dev
+    # the rows past a scene's n_frags: identity as well
+    R = torch.eye(3, dtype=torch.float64, device=dev).repeat(S, Fmax, 1, 1)
+    t = torch.zeros(S, Fmax, 3, dtype=torch.float64, device=dev)
     member = torch.zeros(S, Fmax, dtype=torch.int32, device=dev)
     w_out, res_rot, res_trans = (torch.zeros(S, Emax, dtype=torch.float64, device=dev) for _ in range(3))
     status = torch.zeros(S, dtype=torch.int32, device=dev)
     if S and Fmax:
-        R[:] = torch.eye(3, dtype=torch.float64, device=dev)   # the rows past a scene's n_frags: identity as well
-        t.zero_()
         L = N.lib()
         ws = N.workspace(L.mvr_sync_workspace_bytes(S, Fmax, Emax), dev)
-        N.check(L.mvr_sync_poses(N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), Emax, N.ptr(n_e), N.ptr(n_f), S, Fmax,
-                                 Emax, int(anchor), int(irls_iters), float(c_rot), float(c_trans), N.ptr(R), N.ptr(t),
-                                 Fmax, N.ptr(member), N.ptr(w_out), N.ptr(res_rot), N.ptr(res_trans), N.ptr(status),
-                                 N.ptr(ws), ws.numel(), N.stream()), "mvr_sync_poses")
-    out = {"R": R, "t": t, "member": member, "weights": w_out, "res_rot": res_rot, "res_trans": res_trans,
-           "status": status}
-    if not batched:
-        out = {k: v[0] for k, v in out.items()}
-    if not on_dev:
-        out = {k: v.cpu() for k, v in out.items()}
-        if was_numpy:
-            out = {k: v.numpy() for k, v in out.items()}
-    return out
+        N.check(L.mvr_sync_poses(N.ptr(b.x["R_pair"]), N.ptr(b.x["t_pair"]), N.ptr(b.x["pair"]), N.ptr(b.x["weight"]),
+                                 Emax, N.ptr(b.n_e), N.ptr(b.n_f), S, Fmax, Emax, int(anchor), int(irls_iters),
+                                 float(c_rot), float(c_trans), N.ptr(R), N.ptr(t), Fmax, N.ptr(member), N.ptr(w_out),
+                                 N.ptr(res_rot), N.ptr(res_trans), N.ptr(status), N.ptr(ws), ws.numel(), N.stream()),
+                "mvr_sync_poses")
+    return b.finish({"R": R, "t": t, "member": member, "weights": w_out, "res_rot": res_rot, "res_trans": res_trans,
+                     "status": status})
 
 
 PG_STATUS_NOT_CONNECTED, PG_STATUS_ITERATION_CAP, PG_STATUS_EDGE_IGNORED, PG_STATUS_FACTORISATION = 1, 2, 4, 8
@@ -172,167 +231,62 @@ def optimize_pose_graph(R, t, R_pair, t_pair, pairs, info, weights=None, anchor=
         raise ValueError("optimize_pose_graph: lambda0 must be finite and not negative")
     if not (tol_cost >= 0.0 and tol_step >= 0.0):
         raise ValueError("optimize_pose_graph: the tolerances must not be negative")
-    lists = _as_list(R)
-    first = R if lists is None else (R[0] if len(R) else torch.zeros(0, 3, 3))
-    was_numpy = not torch.is_tensor(first)
-    first = torch.as_tensor(first)
-    on_dev = first.device.type == "cuda"
-    if on_dev:
-        dev = first.device
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        dev = torch.device("cpu")   # the shapes are still checked; require_hip() below then raises
-
-    def f64(x, tail):
-        return torch.as_tensor(x).to(dev, torch.float64).reshape((-1,) + tail)
-
-    if lists is not None:   # per-scene lists -> padded
-        S = len(lists)
-        others = (t, R_pair, t_pair, pairs, info) + (() if weights is None else (weights,)) + \
-            (() if not line_process or uncertain is None else (uncertain,))
-        if any(_as_list(x) is None or len(x) != S for x in others):
-            raise ValueError("optimize_pose_graph: the per-scene lists must have one entry per scene")
-        R0s = [f64(x, (3, 3)) for x in R]
-        Rs = [f64(x, (3, 3)) for x in R_pair]
-        nf, ne = [int(x.shape[0]) for x in R0s], [int(x.shape[0]) for x in Rs]
-        Fmax, Emax = max(nf + [0]), max(ne + [0])
-        R0 = torch.zeros(S, Fmax, 3, 3, dtype=torch.float64, device=dev)
-        t0 = torch.zeros(S, Fmax, 3, dtype=torch.float64, device=dev)
-        Rp = torch.zeros(S, Emax, 3, 3, dtype=torch.float64, device=dev)
-        tp = torch.zeros(S, Emax, 3, dtype=torch.float64, device=dev)
-        ij = torch.zeros(S, Emax, 2, dtype=torch.int32, device=dev)
-        lam = torch.zeros(S, Emax, 36, dtype=torch.float64, device=dev)
-        w = None if weights is None else torch.zeros(S, Emax, dtype=torch.float64, device=dev)
-        unc = None
-        if line_process and uncertain is not None:
-            unc = torch.zeros(S, Emax, dtype=torch.int32, device=dev)
-            for s in range(S):
-                us = torch.as_tensor(uncertain[s]).reshape(-1)
-                if us.shape[0] != ne[s]:
-                    raise ValueError("optimize_pose_graph: scene %d: one uncertain flag per edge" % s)
-                unc[s, :ne[s]] = (us != 0).to(dev, torch.int32)
-        for s in range(S):
-            ts, tps, ijs, ls = f64(t[s], (3,)), f64(t_pair[s], (3,)), torch.as_tensor(pairs[s]).reshape(-1, 2), \
-                f64(info[s], (36,))
-            if ts.shape[0] != nf[s] or not (tps.shape[0] == ijs.shape[0] == ls.shape[0] == ne[s]):
-                raise ValueError("optimize_pose_graph: scene %d: one t per pose and one t_pair, pair and info per "
-                                 "edge" % s)
-            R0[s, :nf[s]], t0[s, :nf[s]] = R0s[s], ts
-            Rp[s, :ne[s]], tp[s, :ne[s]], lam[s, :ne[s]] = Rs[s], tps, ls
-            ij[s, :ne[s]] = ijs.to(dev, torch.int32)
-            if w is not None:
-                ws_ = f64(weights[s], ())
-                if ws_.shape[0] != ne[s]:
-                    raise ValueError("optimize_pose_graph: scene %d: one weight per edge" % s)
-                w[s, :ne[s]] = ws_
-        batched = True
-    else:
-        R0 = torch.as_tensor(R).to(dev, torch.float64)
-        Rp = torch.as_tensor(R_pair).to(dev, torch.float64)
-        if R0.dim() not in (3, 4) or tuple(R0.shape[-2:]) != (3, 3):
-            raise ValueError("optimize_pose_graph: R must be [N,3,3] or [S,F,3,3]")
-        batched = R0.dim() == 4
-        if Rp.dim() != R0.dim() or tuple(Rp.shape[-2:]) != (3, 3):
-            raise ValueError("optimize_pose_graph: R_pair must be [E,3,3] or [S,E,3,3], as R is")
-        if not batched:
-            R0, Rp = R0.unsqueeze(0), Rp.unsqueeze(0)
-        if Rp.shape[0] != R0.shape[0]:
-            raise ValueError("optimize_pose_graph: R and R_pair must hold the same scenes")
-        S, Fmax, Emax = R0.shape[0], R0.shape[1], Rp.shape[1]
-        R0, Rp = R0.contiguous(), Rp.contiguous()
-        try:
-            t0 = torch.as_tensor(t).to(dev, torch.float64).reshape(S, Fmax, 3).contiguous()
-            tp = torch.as_tensor(t_pair).to(dev, torch.float64).reshape(S, Emax, 3).contiguous()
-            ij = torch.as_tensor(pairs).to(dev, torch.int32).reshape(S, Emax, 2).contiguous()
-            lam = torch.as_tensor(info).to(dev, torch.float64).reshape(S, Emax, 36).contiguous()
-            w = None if weights is None else \
-                torch.as_tensor(weights).to(dev, torch.float64).reshape(S, Emax).contiguous()
-            unc = None if not line_process or uncertain is None else \
-                (torch.as_tensor(uncertain).to(dev) != 0).to(torch.int32).reshape(S, Emax).contiguous()
-        except RuntimeError:
-            raise ValueError("optimize_pose_graph: t must hold one row per pose; t_pair, pairs, info, weights and "
-                             "uncertain one per edge") from None
-        nf = [Fmax] * S if n_frags is None else [int(v) for v in torch.as_tensor(n_frags).reshape(-1).tolist()]
-        ne = [Emax] * S if n_edges is None else [int(v) for v in torch.as_tensor(n_edges).reshape(-1).tolist()]
-        if len(nf) != S or min(nf + [0]) < 0 or max(nf + [0]) > Fmax:
-            raise ValueError("optimize_pose_graph: n_frags must be [S] with 0 <= n_frags <= F")
-        if len(ne) != S or min(ne + [0]) < 0 or max(ne + [0]) > Emax:
-            raise ValueError("optimize_pose_graph: n_edges must be [S] with 0 <= n_edges <= E")
-    if Fmax > MAX_FRAGS:
-        raise ValueError("optimize_pose_graph: at most %d fragments per scene" % MAX_FRAGS)
-    if not 0 <= int(anchor) < max(Fmax, 1):
-        raise ValueError("optimize_pose_graph: anchor outside the fragments")
+    b = _scene_batch("optimize_pose_graph",
+                     _edge_fields(R_pair, t_pair, pairs, weights) + (
+                         ("info", info, (36,), torch.float64, False),
+                         ("uncertain flag", uncertain if line_process else None, (), FLAG, True)),
+                     (("R", R, (3, 3), torch.float64, False), ("t", t, (3,), torch.float64, False)),
+                     n_frags, n_edges, anchor, R)
     N.require_hip()
-    rows = int(max_iters) + 1
-    n_e = torch.tensor(ne, dtype=torch.int32).to(dev)
-    n_f = torch.tensor(nf, dtype=torch.int32).to(dev)
+    S, Fmax, Emax, dev = b.S, b.Fmax, b.Emax, b.dev
+    Rp, tp, ij, w, lam, unc, R0, t0 = (b.x[k] for k in ("R_pair", "t_pair", "pair", "weight", "info",
+                                                         "uncertain flag", "R", "t"))
     Ro, to = R0.clone(), t0.clone()      # the rows past a scene's n_frags keep their input
     member = torch.zeros(S, Fmax, dtype=torch.int32, device=dev)
     cost = torch.zeros(S, 2, dtype=torch.float64, device=dev)
     iters, status = (torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2))
-    trace = torch.full((S, rows), -1.0, dtype=torch.float64, device=dev) if return_trace else None
-    if line_process:
-        L = N.lib()
-        line = torch.zeros(S, Emax, dtype=torch.float64, device=dev)
-        kept = torch.ones(S, Emax, dtype=torch.bool, device=dev)
-        mu = torch.zeros(S, dtype=torch.float64, device=dev)
-        passes = []
-        w = torch.ones(S, Emax, dtype=torch.float64, device=dev) if w is None else w.clone()
-        flag = torch.ones(S, Emax, dtype=torch.bool, device=dev) if unc is None else unc != 0
-        live = torch.arange(Emax, device=dev)[None, :] < n_e[:, None].to(torch.int64)
-        for p in range(max(int(prune_passes), 1)):
-            if p:
-                R0, t0 = Ro.clone(), to.clone()
-            l_p = torch.zeros(S, Emax, dtype=torch.float64, device=dev)
-            if S and Fmax:
-                ws = N.workspace(L.mvr_posegraph_lp_workspace_bytes(S, Fmax, Emax), dev)
-                N.check(L.mvr_posegraph_optimize_lp(
-                    N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(lam), N.ptr(unc), Emax, N.ptr(n_e), N.ptr(n_f), S,
-                    Fmax, Emax, int(anchor), N.ptr(R0), N.ptr(t0), int(max_iters), float(lambda0), float(tol_cost),
-                    float(tol_step), mu_scale, N.ptr(Ro), N.ptr(to), Fmax, N.ptr(member), N.ptr(cost), N.ptr(iters),
-                    N.ptr(status), N.ptr(trace), N.ptr(l_p), N.ptr(mu), N.ptr(ws), ws.numel(), N.stream()),
-                    "mvr_posegraph_optimize_lp")
-            passes.append({"iters": iters.clone(), "status": status.clone(), "cost": cost.clone()})
-            counted = (l_p > 0.0) & live             # a counted edge's l is positive (1 for a certain one)
-            line = torch.where(counted, l_p, line)
-            if int(prune_passes) > 0:
-                drop = counted & flag & (l_p < float(edge_prune_threshold))
-                w = torch.where(drop, torch.zeros_like(w), w)
-                kept &= ~drop
-        out = {"R": Ro, "t": to, "member": member, "cost": cost, "iters": iters, "status": status}
-        if return_trace:
-            out["trace"] = trace
-        out.update(line=line, kept=kept, mu=mu)
-
-        def shape(d):
-            if not batched:
-                d = {k: v[0] for k, v in d.items()}
-            if not on_dev:
-                d = {k: v.cpu() for k, v in d.items()}
-                if was_numpy:
-                    d = {k: v.numpy() for k, v in d.items()}
-            return d
-        out = shape(out)
-        out["passes"] = [shape(d) for d in passes]
-        return out
-    if S and Fmax:
-        L = N.lib()
-        ws = N.workspace(L.mvr_posegraph_workspace_bytes(S, Fmax, Emax), dev)
-        N.check(L.mvr_posegraph_optimize(N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(lam), Emax, N.ptr(n_e),
-                                         N.ptr(n_f), S, Fmax, Emax, int(anchor), N.ptr(R0), N.ptr(t0),
-                                         int(max_iters), float(lambda0), float(tol_cost), float(tol_step), N.ptr(Ro),
-                                         N.ptr(to), Fmax, N.ptr(member), N.ptr(cost), N.ptr(iters), N.ptr(status),
-                                         N.ptr(trace), N.ptr(ws), ws.numel(), N.stream()), "mvr_posegraph_optimize")
     out = {"R": Ro, "t": to, "member": member, "cost": cost, "iters": iters, "status": status}
     if return_trace:
-        out["trace"] = trace
-    if not batched:
-        out = {k: v[0] for k, v in out.items()}
-    if not on_dev:
-        out = {k: v.cpu() for k, v in out.items()}
-        if was_numpy:
-            out = {k: v.numpy() for k, v in out.items()}
+        out["trace"] = torch.full((S, int(max_iters) + 1), -1.0, dtype=torch.float64, device=dev)
+    trace = out.get("trace")
+    L = N.lib() if S and Fmax else None      # nothing to launch otherwise
+    if not line_process:
+        if L is not None:
+            ws = N.workspace(L.mvr_posegraph_workspace_bytes(S, Fmax, Emax), dev)
+            N.check(L.mvr_posegraph_optimize(
+                N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(lam), Emax, N.ptr(b.n_e), N.ptr(b.n_f), S, Fmax, Emax,
+                int(anchor), N.ptr(R0), N.ptr(t0), int(max_iters), float(lambda0), float(tol_cost), float(tol_step),
+                N.ptr(Ro), N.ptr(to), Fmax, N.ptr(member), N.ptr(cost), N.ptr(iters), N.ptr(status), N.ptr(trace),
+                N.ptr(ws), ws.numel(), N.stream()), "mvr_posegraph_optimize")
+        return b.finish(out)
+    line = torch.zeros(S, Emax, dtype=torch.float64, device=dev)
+    kept = torch.ones(S, Emax, dtype=torch.bool, device=dev)
+    mu = torch.zeros(S, dtype=torch.float64, device=dev)
+    passes = []
+    w = torch.ones(S, Emax, dtype=torch.float64, device=dev) if w is None else w.clone()
+    flag = torch.ones(S, Emax, dtype=torch.bool, device=dev) if unc is None else unc != 0
+    live = torch.arange(Emax, device=dev)[None, :] < b.n_e[:, None].to(torch.int64)
+    for p in range(max(int(prune_passes), 1)):
+        if p:
+            R0, t0 = Ro.clone(), to.clone()
+        l_p = torch.zeros(S, Emax, dtype=torch.float64, device=dev)
+        if L is not None:
+            ws = N.workspace(L.mvr_posegraph_lp_workspace_bytes(S, Fmax, Emax), dev)
+            N.check(L.mvr_posegraph_optimize_lp(
+                N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(lam), N.ptr(unc), Emax, N.ptr(b.n_e), N.ptr(b.n_f), S,
+                Fmax, Emax, int(anchor), N.ptr(R0), N.ptr(t0), int(max_iters), float(lambda0), float(tol_cost),
+                float(tol_step), mu_scale, N.ptr(Ro), N.ptr(to), Fmax, N.ptr(member), N.ptr(cost), N.ptr(iters),
+                N.ptr(status), N.ptr(trace), N.ptr(l_p), N.ptr(mu), N.ptr(ws), ws.numel(), N.stream()),
+                "mvr_posegraph_optimize_lp")
+        passes.append({"iters": iters.clone(), "status": status.clone(), "cost": cost.clone()})
+        counted = (l_p > 0.0) & live             # a counted edge's l is positive (1 for a certain one)
+        line = torch.where(counted, l_p, line)
+        if int(prune_passes) > 0:
+            drop = counted & flag & (l_p < float(edge_prune_threshold))
+            w = torch.where(drop, torch.zeros_like(w), w)
+            kept &= ~drop
+    out = b.finish(dict(out, line=line, kept=kept, mu=mu))
+    out["passes"] = [b.finish(p) for p in passes]
     return out
 
 

@@ -395,7 +395,28 @@ def zero_info(only_edge, seed=1):
     return sc
 
 
-EDGE_COUNTS = (0, 1, 127, 128, 129, 255, 256, 257)     # the kernel stages the edges' endpoints in chunks of 256
+def cut_by_bad_edge(seed=1):
+    """3 fragments on the chain (0,1), (1,2) whose second edge has a NaN in its rotation, plus a self-loop (2,2): the
+    ignored edge is the only way to fragment 2, so the edge test decides the component"""
+    sc = scene(3, seed, "all", True, 0)
+    keep = [e for e, (i, j) in enumerate(sc["ij"]) if (i, j) in ((0, 1), (1, 2))]
+    assert len(keep) == 2
+    for k in ("R_pair", "t_pair", "ij", "info", "w"):
+        sc[k] = np.concatenate([sc[k][keep], sc[k][keep[1:]]])
+    sc["R_pair"][1, 0, 2] = np.nan
+    sc["ij"][2] = (2, 2)
+    return sc
+
+
+def n1_bad_edges():
+    """1 fragment with two edges that cannot count, (0,0) and (0,1), unit weights: nothing to optimise, status 4"""
+    sc = scene(1, 1)
+    sc.update(R_pair=np.tile(np.eye(3), (2, 1, 1)), t_pair=np.zeros((2, 3)), ij=np.array([[0, 0], [0, 1]], np.int64),
+              info=np.tile(np.eye(6), (2, 1, 1)), w=np.ones(2))
+    return sc
+
+
+EDGE_COUNTS = (0, 1, 127, 128, 129, 255, 256, 257)    # the kernel stages the edges' endpoints in chunks of 256
 TWO = dict(max_iters=2, tol_cost=0.0, tol_step=0.0)
 STEP = dict(tol_cost=0.0, tol_step=1e-4)     # exact edges: the third trial's step is 3e-10 .. 2e-5, the second's > 1e-3
 
@@ -426,7 +447,9 @@ def cases():
            "disconnected": (disconnected(), TWO),
            "anchor3": (scene(8, 1, "all", True, 2), dict(TWO, anchor=3)),
            "zero_info": (zero_info(False), TWO),
-           "zero_info_only_edge": (zero_info(True), dict(max_iters=4))}
+           "zero_info_only_edge": (zero_info(True), dict(max_iters=4)),
+           "cut_by_bad_edge": (cut_by_bad_edge(), TWO),
+           "n1_bad_edges": (n1_bad_edges(), {})}
     full = scene(24, 1, "all", True, 0)
     for E in EDGE_COUNTS:
         out["edges_%d" % E] = (truncated(full, E), TWO)

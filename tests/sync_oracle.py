@@ -217,6 +217,19 @@ def _with_bad_edges(scene):
     return s
 
 
+def _cut_by_bad_edge(scene):
+    """a chain (0,1), (1,2) whose second edge gets a NaN in its rotation, and a self-loop (2,2) appended: the ignored
+    edge is the only way to fragment 2, so the edge test decides the component"""
+    s = dict(scene)
+    s["R_pair"] = np.concatenate([scene["R_pair"], np.eye(3)[None]])
+    s["R_pair"][1, 0, 2] = np.nan
+    s["t_pair"] = np.concatenate([scene["t_pair"], np.zeros((1, 3))])
+    s["ij"] = np.concatenate([scene["ij"], np.array([[2, 2]])])
+    s["w"] = np.concatenate([scene["w"], np.ones(1)])
+    s["outlier"] = np.concatenate([scene["outlier"], np.zeros(1, bool)])
+    return s
+
+
 CASES = {
     # name: (scene constructor, irls passes)
     "n2": (lambda: make_scene(2, [(0, 1)], 1), 0),
@@ -231,11 +244,16 @@ CASES = {
     # fragments {0,1,2} and {3,4,5} form two components, 6 and 7 are isolated
     "two_components": (lambda: make_scene(8, [(0, 1), (1, 2), (2, 0), (3, 4), (4, 5), (5, 3)], 10), 0),
     "bad_edges": (lambda: _with_bad_edges(make_scene(6, complete_edges(6), 12, 0.02, 0.02)), 0),
+    "cut_by_bad_edge": (lambda: _cut_by_bad_edge(make_scene(3, [(0, 1), (1, 2)], 15, 0.02, 0.02)), 2),
     "complete64": (lambda: make_scene(64, complete_edges(64), 9, 0.02, 0.02, random_weights=True), 0),
     # either side of the kernel's switch from the LDS-resident to the workspace-resident matrix (max_frags 42 | 43)
     "complete42": (lambda: make_scene(42, complete_edges(42), 13, 0.02, 0.02, random_weights=True), 0),
     "complete43": (lambda: make_scene(43, complete_edges(43), 14, 0.02, 0.02, random_weights=True), 0),
 }
+# one fragment with two edges that cannot count, (0,0) and (0,1): status 4, nothing solved.  Not in CASES: a single
+# fragment has no spectrum
+N1_BAD_EDGES = {"n": 1, "anchor": 0, "R_pair": np.tile(np.eye(3), (2, 1, 1)), "t_pair": np.zeros((2, 3)),
+                "ij": np.array([[0, 0], [0, 1]], np.int64), "w": np.ones(2)}
 NOISE_FREE = ("n2", "n3", "complete30", "ring12", "chain12_reversed")
 OUTLIER_BOUND = 0.05   # the outlier scenes: 5 IRLS passes land within it, 0 passes do not
 

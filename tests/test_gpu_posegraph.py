@@ -150,6 +150,26 @@ def test_python_surface(gpu):
     f64 = optimize_pose_graph(*(x.astype(np.float32).astype(np.float64) if x.dtype == np.float64 else x for x in a),
                               **kw)
     assert f32["R"].dtype == np.float64 and f32["R"].tobytes() == f64["R"].tobytes()
+    # the three input forms: per-scene lists, a padded batch with n_frags / n_edges, and each scene alone
+    scs = [PO.cases()[n][0] for n in ("n2_exact", "n3_noisy", "cut_by_bad_edge")]
+    nf, ne = [len(s["R0"]) for s in scs], [len(s["ij"]) for s in scs]
+    keys = ("R0", "t0", "R_pair", "t_pair", "ij", "info", "w")
+    lists = optimize_pose_graph(*([s[k] for s in scs] for k in keys), **PO.TWO)
+
+    def padded(k):
+        count = nf if k in ("R0", "t0") else ne
+        out = np.full((3, max(count)) + scs[0][k].shape[1:], 7, scs[0][k].dtype)   # the padding is never read
+        for i, s in enumerate(scs):
+            out[i, :count[i]] = s[k]
+        return out
+    pad = optimize_pose_graph(*(padded(k) for k in keys), n_frags=nf, n_edges=ne, **PO.TWO)
+    assert lists["status"].tolist() == [0, 0, 5] and lists["member"][2].tolist() == [1, 1, 0]
+    for i, s in enumerate(scs):
+        alone = optimize_pose_graph(*(s[k] for k in keys), **PO.TWO)
+        for k in alone:
+            n = nf[i] if k in ("R", "t", "member") else None
+            x, y = (np.ascontiguousarray(o[k][i] if n is None else o[k][i, :n]) for o in (lists, pad))
+            assert x.tobytes() == y.tobytes() == alone[k].tobytes(), (i, k)
     empty = optimize_pose_graph([], [], [], [], [], [])
     assert empty["R"].shape == (0, 0, 3, 3) and empty["status"].shape == (0,)
 

@@ -78,7 +78,7 @@ def test_noise_free_recovery(gpu, name):
     assert er <= TOL and et <= TOL and got["status"] == 0 and got["member"].all()
 
 
-@pytest.mark.parametrize("name", ["complete30_noisy", "ring12_noisy"])
+@pytest.mark.parametrize("name", ["complete30_noisy", "ring12_noisy", "cut_by_bad_edge"])
 def test_noisy_scene_matches_oracle(gpu, name):
     sc, got, want = gpu_case(gpu, name)
     assert_matches_oracle(got, want, name)
@@ -139,7 +139,7 @@ def test_anchor_outside_the_scene(gpu):
 def test_batch_is_bit_equal_to_single_scenes(gpu):
     one = {"n": 1, "anchor": 0, "R_pair": np.zeros((0, 3, 3)), "t_pair": np.zeros((0, 3)),
            "ij": np.zeros((0, 2), np.int64), "w": np.zeros(0)}
-    scenes = [O.case("ring12_noisy")[0], one, O.case("outliers30")[0]]
+    scenes = [O.case("ring12_noisy")[0], one, O.case("outliers30")[0], O.N1_BAD_EDGES]
     batch = run_gpu(gpu, scenes, irls=2)
     assert batch[1]["status"] == 0 and batch[1]["member"].tolist() == [1]
     assert np.array_equal(batch[1]["R"][0], np.eye(3)) and not batch[1]["t"].any()
@@ -150,6 +150,12 @@ def test_batch_is_bit_equal_to_single_scenes(gpu):
             assert np.array_equal(alone[key], batch[k][key]), (k, key)
     want = O.sync_oracle(scenes[0]["R_pair"], scenes[0]["t_pair"], scenes[0]["ij"], 12, scenes[0]["w"], irls_iters=2)
     assert_matches_oracle(batch[0], want, "ring12_noisy in a batch, irls 2")
+    # one fragment with edges that cannot count: between the edge test and the single-fragment return
+    bad = scenes[3]
+    want = O.sync_oracle(bad["R_pair"], bad["t_pair"], bad["ij"], 1, bad["w"], irls_iters=2)
+    assert want["status"] == 4 and batch[3]["status"] == 4 and batch[3]["member"].tolist() == [1]
+    assert_matches_oracle(batch[3], want, "n1_bad_edges in a batch, irls 2")
+    assert not batch[3]["weights"].any() and np.array_equal(batch[3]["R"][0], np.eye(3)) and not batch[3]["t"].any()
 
 
 @pytest.mark.parametrize("name", ["complete64", "complete42", "complete43"])
@@ -202,3 +208,22 @@ def test_python_surface_fp32_inputs(gpu):
     want = O.case("ring12_noisy")[2]
     assert np.abs(both["R"][1, :12] - want["R"]).max() <= TOL and np.abs(both["t"][1, :12] - want["t"]).max() <= TOL
     assert np.array_equal(both["R"][1, 12:], np.tile(np.eye(3), (18, 1, 1)))
+    # the three input forms: per-scene lists, a padded batch with n_edges, and each scene alone, byte for byte
+    scs = [O.case(n)[0] for n in ("n2", "n3", "cut_by_bad_edge")]
+    nf, ne = [s["n"] for s in scs], [len(s["ij"]) for s in scs]
+    keys = ("R_pair", "t_pair", "ij")
+    lists = synchronize(*([s[k] for s in scs] for k in keys), nf, weights=[s["w"] for s in scs], irls_iters=2)
+
+    def padded(k):
+        out = np.full((3, max(ne)) + scs[0][k].shape[1:], 7, scs[0][k].dtype)    # the padding is never read
+        for i, s in enumerate(scs):
+            out[i, :ne[i]] = s[k]
+        return out
+    pad = synchronize(*(padded(k) for k in keys), nf, weights=padded("w"), irls_iters=2, n_edges=ne)
+    assert lists["status"].tolist() == [0, 0, 5] and lists["member"].tolist() == [[1, 1, 0], [1, 1, 1], [1, 1, 0]]
+    for i, s in enumerate(scs):
+        alone = synchronize(*(s[k] for k in keys), nf[i], weights=s["w"], irls_iters=2)
+        for k in ("R", "t", "member", "weights", "status"):
+            n = {"R": nf[i], "t": nf[i], "member": nf[i], "weights": ne[i]}.get(k)
+            a, b = (np.ascontiguousarray(x[k][i] if n is None else x[k][i, :n]) for x in (lists, pad))
+            assert a.tobytes() == b.tobytes() == alone[k].tobytes(), (i, k)

@@ -124,6 +124,12 @@ def test_case_statuses_are_what_their_names_say():
     z = res["zero_info_only_edge"]                    # the fragment's block of H is exactly zero: pivot 0, every trial
     assert z["failed"] == [True] * 4 and z["status"] == (2 | 8) and z["cost"][0] == z["cost"][1]
     assert PO.run(PO.cases()["zero_info_only_edge"][0], max_iters=4, solver="solve")["failed"] == [True] * 4
+    # the edge test decides the component: the ignored edge was the only way to fragment 2
+    cut = res["cut_by_bad_edge"]
+    assert cut["status"] == 5 and cut["member"].tolist() == [1, 1, 0] and cut["accepted"] == [True, True]
+    assert min(m[0] for m in cut["margins"]) >= 0.999
+    one = res["n1_bad_edges"]
+    assert one["status"] == 4 and one["member"].tolist() == [1] and one["iters"] == 0 and not one["cost"].any()
     # invalid scenes
     sc = PO.cases()["n3_noisy"][0]
     inv = PO.run(sc, anchor=3)

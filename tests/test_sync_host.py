@@ -153,6 +153,42 @@ def test_oracle_edge_cases():
     assert out["status"] == 4 and clean["status"] == 0
     assert np.array_equal(out["R"], clean["R"]) and np.array_equal(out["t"], clean["t"])
     assert not out["weights"][-2:].any() and not out["res_rot"][-2:].any()
+    # the ignored edge was the only way to fragment 2: the edge test decides the component
+    cut = O.case("cut_by_bad_edge")[2]
+    assert cut["status"] == 5 and cut["member"].tolist() == [1, 1, 0] and cut["weights"].tolist() == [1.0, 0.0, 0.0]
+    # one fragment, two edges that cannot count: on the seam between the edge test and the single-fragment return
+    sc = O.N1_BAD_EDGES
+    n1 = O.sync_oracle(sc["R_pair"], sc["t_pair"], sc["ij"], 1, sc["w"])
+    assert n1["status"] == 4 and n1["member"].tolist() == [1] and not n1["weights"].any()
+    assert np.array_equal(n1["R"][0], np.eye(3)) and not n1["t"].any()
+
+
+def test_wrapper_argument_rules_without_a_device():
+    """every shape and count rule of synchronize is a ValueError, raised before a device is asked for"""
+    from lib.multiview import synchronize
+    sc = O.make_scene(4, O.complete_edges(4)[:5], seed=23)
+    R, t, ij = sc["R_pair"], sc["t_pair"], sc["ij"]
+    assert len(ij) == 5
+    for args, kw in ((([R], [t, t], [ij], [4]), {}),                          # per-scene lists of unequal length
+                     (([R], [t], [ij], [4]), dict(weights=[sc["w"], sc["w"]])),
+                     (([R], [t[:1]], [ij], [4]), {}),                         # one t_pair row for five edges
+                     (([R], [t], [ij], [4]), dict(weights=[np.ones(1)])),     # one weight for five edges
+                     (([R], [t], [ij[:-1]], [4]), {}),                        # pairs with a row short
+                     ((R, t, ij[:-1], 4), {}),
+                     ((R[None], t[None], ij[None, :-1], [4]), {}),
+                     ((R, t[:1], ij, 4), {}),
+                     ((R, t, ij, 4), dict(weights=np.ones(1))),
+                     ((R.reshape(-1, 9), t, ij, 4), {}),                      # R_pair [E,9]
+                     ((R[None], t[None], ij[None], [4, 4]), {}),              # n_frags of the wrong length
+                     (([R], [t], [ij], [4, 4]), {}),
+                     ((R[None], t[None], ij[None], [4]), dict(n_edges=[6])),  # n_edges above E
+                     ((R[None], t[None], ij[None], [4]), dict(n_edges=[5, 5])),
+                     ((R, t, ij, 129), {}),                                   # n_frags above MAX_FRAGS
+                     ((R, t, ij, -1), {}),
+                     ((R, t, ij, 4), dict(anchor=4)),                         # anchor outside
+                     ((R, t, ij, 4), dict(anchor=-1))):
+        with pytest.raises(ValueError, match="synchronize: "):
+            synchronize(*args, **kw)
 
 
 # ------------------------------------------------------------------- the input conditions the GPU tests rely on

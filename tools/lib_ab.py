@@ -1,0 +1,213 @@
+"""Byte comparison of two builds of the library on what shared device code computes.  The oracles pin selections bit for
+bit but fits and solves to 1e-9 only; a change that must not move a bit is shown against the build before it (DESIGN.md
+4.26, 4.31).
+For each library one fresh child process (MVR_LIB selects the library) runs the chosen case sets through the C ABI and
+writes every output, allocated full of a sentinel, to an .npz; this process, which never opens the GPU, then compares
+the two files key by key with tobytes().  The case sets:
+  ransac  csrc/ransac.hpp's users and common.hpp's block_max under mvr_fgr:
+    * mvr_ransac with hyp_out at ransac_n 3, 4 and 8 over tests/test_gpu_ransac_checked.py's anchor inputs
+      (parity_inputs(300) at 256 iterations, parity_inputs(37) at 100, plus a pair of 2 rows);
+    * mvr_ransac_checked on the same, checkers off (cap = iterations) and edge 0.9 + distance 0.05 at cap 64;
+    * mvr_fgr at its defaults on tests/fgr_oracle.py's batch, tuple filter on and off, with the trace.
+  graph   csrc/scene.hpp's users:
+    * mvr_sync_poses on every scene of tests/sync_oracle.py's CASES at its own IRLS passes (both instantiations:
+      42 | 43 | 64 fragments), plus one ragged batch at 2 passes;
+    * mvr_posegraph_optimize on every entry of tests/posegraph_oracle.py's cases() with the trace;
+    * mvr_posegraph_optimize_lp on the same, with `uncertain` NULL and with every edge flagged uncertain.
+usage: python tools/lib_ab.py LIB_A LIB_B [--cases ransac,graph] [--keep DIR]     exit status 0: every key identical"""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "3d_multiview_reg_amd"), os.path.join(ROOT, "tests"),
+          os.path.join(ROOT, "tests", "golden")):
+    sys.path.insert(0, p)
+import numpy as np  # noqa: E402
+
+SENT = -77
+SHAPES = [(300, 256), (37, 100)]
+
+
+def filled(d):
+    """allocators of sentinel-filled fp64 / int32 device tensors: what a build does not write shows as such"""
+    import torch
+    return (lambda *s: torch.full(s, float(SENT), dtype=torch.float64, device=d),
+            lambda *s: torch.full(s, SENT, dtype=torch.int32, device=d))
+
+
+def child(out_path, sets):
+    import torch
+    from lib import _native as N
+    out = {}
+
+    def keep(tag, o):
+        torch.cuda.synchronize()
+        for k, v in o.items():
+            out[tag + " " + k] = v.cpu().numpy()
+    for name in sets:
+        CASE_SETS[name](torch.device("cuda"), N.lib(), keep)
+    np.savez(out_path, **out)
+    print("%s (%s): %s, %d arrays" % (N.LIB_PATH, N.source_hash(), ", ".join(sets), len(out)), flush=True)
+
+
+def ransac_cases(d, L, keep):
+    import torch
+    import fgr_oracle as F
+    import ransac_checked_oracle as C
+    from lib import _native as N
+    f64, i32 = filled(d)
+    for n, iters in SHAPES:
+        (x1, x2), counts = C.parity_inputs(n)
+        counts = counts + [2]
+        x1, x2 = np.concatenate([x1, x1[:1]]), np.concatenate([x2, x2[:1]])
+        P = len(counts)
+        X1, X2 = torch.from_numpy(x1).to(d), torch.from_numpy(x2).to(d)
+        cnt = torch.tensor(counts, dtype=torch.int32, device=d)
+        for rn in (3, 4, 8):
+            # rows of a pair below ransac_n keep the sentinel in hyp: written by neither build
+            o = {"T": f64(P, 4, 4), "fitness": f64(P), "rmse": f64(P), "best_iter": i32(P), "hyp": f64(P, iters, 12)}
+            ws = torch.empty(L.mvr_ransac_workspace_bytes(P, iters), dtype=torch.uint8, device=d)
+            N.check(L.mvr_ransac(N.ptr(X1), N.ptr(X2), n * 3, N.ptr(cnt), P, rn, iters, C.MAX_DIST, C.SEED,
+                                 N.ptr(o["T"]), N.ptr(o["fitness"]), N.ptr(o["rmse"]), N.ptr(o["best_iter"]),
+                                 N.ptr(o["hyp"]), N.ptr(ws), ws.numel(), N.stream()), "mvr_ransac")
+            keep("ransac n%d i%d k%d" % (n, iters, rn), o)
+            for mode, edge, dist, cap in (("off", 0.0, 0.0, iters), ("edge+dist", 0.9, C.MAX_DIST, 64)):
+                nw = (iters + 63) // 64
+                o = {"T": f64(P, 4, 4), "fitness": f64(P), "rmse": f64(P), "best_iter": i32(P), "n_pass": i32(P),
+                     "n_valid": i32(P), "words": torch.full((P, nw), SENT, dtype=torch.int64, device=d),
+                     "valid": i32(P, cap), "hyp": f64(P, cap, 12)}
+                ws = torch.empty(L.mvr_ransac_checked_workspace_bytes(P, iters, cap), dtype=torch.uint8, device=d)
+                N.check(L.mvr_ransac_checked(N.ptr(X1), N.ptr(X2), n * 3, N.ptr(cnt), P, rn, iters, C.MAX_DIST,
+                                             C.SEED, cap, edge, dist, None, None, -1.0, N.ptr(o["T"]),
+                                             N.ptr(o["fitness"]), N.ptr(o["rmse"]), N.ptr(o["best_iter"]),
+                                             N.ptr(o["n_pass"]), N.ptr(o["n_valid"]), N.ptr(o["words"]),
+                                             N.ptr(o["valid"]), N.ptr(o["hyp"]), N.ptr(ws), ws.numel(), N.stream()),
+                        "mvr_ransac_checked")
+                keep("checked %s n%d i%d k%d" % (mode, n, iters, rn), o)
+
+    x1, x2, counts = F.batch()
+    P, n = x1.shape[0], x1.shape[1]
+    X1, X2 = torch.from_numpy(x1.copy()).to(d), torch.from_numpy(x2.copy()).to(d)   # the batch is read-only
+    cnt = torch.from_numpy(counts).to(d)
+    q = F.DEFAULTS
+    for tuple_test in (True, False):
+        o = {"T": f64(P, 4, 4), "fitness": f64(P), "rmse": f64(P), "n_used": i32(P), "n_tuples": i32(P),
+             "status": i32(P), "trace": f64(P, q["iters"], 2)}
+        ws = torch.empty(L.mvr_fgr_workspace_bytes(P, n, q["max_tuples"]), dtype=torch.uint8, device=d)
+        N.check(L.mvr_fgr(N.ptr(X1), N.ptr(X2), 3 * n, N.ptr(cnt), P, q["max_dist"], q["iters"], q["division_factor"],
+                          q["tuple_factor"] if tuple_test else 0, q["max_tuples"], q["tuple_scale"], F.SEED,
+                          N.ptr(o["T"]), N.ptr(o["fitness"]), N.ptr(o["rmse"]), N.ptr(o["n_used"]),
+                          N.ptr(o["n_tuples"]), N.ptr(o["status"]), N.ptr(o["trace"]), N.ptr(ws), ws.numel(),
+                          N.stream()), "mvr_fgr")
+        keep("fgr tuple_test=%s" % tuple_test, o)
+
+
+def graph_cases(d, L, keep):
+    import torch
+    import posegraph_oracle as PO
+    import sync_oracle as SO
+    from lib import _native as N
+    f64, i32 = filled(d)
+
+    def padded(scenes, key, dtype=None):
+        """[S, max count, ...] of the scenes' arrays `key`, zero padded, on the device"""
+        tail = np.shape(scenes[0][key])[1:]
+        x = np.zeros((len(scenes), max(len(s[key]) for s in scenes)) + tail, dtype or np.float64)
+        for k, s in enumerate(scenes):
+            x[k, :len(s[key])] = s[key]
+        return torch.from_numpy(x).to(d)
+
+    def counts(scenes, key):
+        return torch.tensor([len(s[key]) if key != "n" else s["n"] for s in scenes], dtype=torch.int32, device=d)
+
+    def sync(tag, scenes, anchor, irls):
+        Rp, tp, ij, w = (padded(scenes, "R_pair"), padded(scenes, "t_pair"), padded(scenes, "ij", np.int32),
+                         padded(scenes, "w"))
+        S, E, F = len(scenes), Rp.shape[1], max(s["n"] for s in scenes)
+        o = {"R": f64(S, F, 9), "t": f64(S, F, 3), "member": i32(S, F), "weights": f64(S, E), "res_rot": f64(S, E),
+             "res_trans": f64(S, E), "status": i32(S)}
+        ws = torch.empty(L.mvr_sync_workspace_bytes(S, F, E), dtype=torch.uint8, device=d)
+        N.check(L.mvr_sync_poses(N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), E, N.ptr(counts(scenes, "ij")),
+                                 N.ptr(counts(scenes, "n")), S, F, E, anchor, irls, 0.1, 0.1, N.ptr(o["R"]),
+                                 N.ptr(o["t"]), F, N.ptr(o["member"]), N.ptr(o["weights"]), N.ptr(o["res_rot"]),
+                                 N.ptr(o["res_trans"]), N.ptr(o["status"]), N.ptr(ws), ws.numel(), N.stream()),
+                "mvr_sync_poses")
+        keep(tag, o)
+
+    for name in sorted(SO.CASES):
+        sc = SO.CASES[name][0]()
+        sync("sync " + name, [sc], sc["anchor"], SO.CASES[name][1])
+    sync("sync ragged batch", [SO.CASES[n][0]() for n in ("ring12_noisy", "cut_by_bad_edge", "outliers30", "n2")] +
+         [SO.N1_BAD_EDGES], 0, 2)
+
+    for name, (sc, kw) in sorted(PO.cases().items()):
+        scs = [sc]
+        Rp, tp, ij, w, info = (padded(scs, "R_pair"), padded(scs, "t_pair"), padded(scs, "ij", np.int32),
+                               padded(scs, "w"), padded(scs, "info"))
+        R0, t0 = padded(scs, "R0"), padded(scs, "t0")
+        F, E, iters = R0.shape[1], Rp.shape[1], kw.get("max_iters", 20)
+        n_e, n_f = counts(scs, "ij"), counts(scs, "R0")
+        settings = (iters, kw.get("lambda0", 1e-6), kw.get("tol_cost", 1e-9), kw.get("tol_step", 1e-10))
+        for mode, unc in (("plain", None), ("lp", None), ("lp all uncertain", torch.ones(1, E, dtype=torch.int32,
+                                                                                         device=d))):
+            o = {"R": f64(1, F, 9), "t": f64(1, F, 3), "member": i32(1, F), "cost": f64(1, 2), "iters": i32(1),
+                 "status": i32(1), "trace": f64(1, iters + 1)}
+            head = (N.ptr(Rp), N.ptr(tp), N.ptr(ij), N.ptr(w), N.ptr(info))
+            mid = (E, N.ptr(n_e), N.ptr(n_f), 1, F, E, kw.get("anchor", 0), N.ptr(R0), N.ptr(t0)) + settings
+            res = (N.ptr(o["R"]), N.ptr(o["t"]), F, N.ptr(o["member"]), N.ptr(o["cost"]), N.ptr(o["iters"]),
+                   N.ptr(o["status"]), N.ptr(o["trace"]))
+            if mode == "plain":
+                ws = torch.empty(L.mvr_posegraph_workspace_bytes(1, F, E), dtype=torch.uint8, device=d)
+                N.check(L.mvr_posegraph_optimize(*head, *mid, *res, N.ptr(ws), ws.numel(), N.stream()),
+                        "mvr_posegraph_optimize")
+            else:
+                o.update(line=f64(1, E), mu=f64(1))
+                ws = torch.empty(L.mvr_posegraph_lp_workspace_bytes(1, F, E), dtype=torch.uint8, device=d)
+                N.check(L.mvr_posegraph_optimize_lp(*head, N.ptr(unc), *mid, 0.0025, *res, N.ptr(o["line"]),
+                                                    N.ptr(o["mu"]), N.ptr(ws), ws.numel(), N.stream()),
+                        "mvr_posegraph_optimize_lp")
+            keep("posegraph %s %s" % (mode, name), o)
+
+
+CASE_SETS = {"ransac": ransac_cases, "graph": graph_cases}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("libs", nargs="*")
+    ap.add_argument("--cases", default=",".join(CASE_SETS), help="case sets, comma separated (default: %(default)s)")
+    ap.add_argument("--keep", help="directory for the two .npz files (default: a temporary one)")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    sets = a.cases.split(",")
+    if not sets or any(c not in CASE_SETS for c in sets):
+        ap.error("--cases: a comma separated choice of " + ", ".join(CASE_SETS))
+    if a.child:
+        return child(a.child, sets)
+    if len(a.libs) != 2:
+        ap.error("two libraries")
+    with tempfile.TemporaryDirectory() as tmp:
+        where = a.keep or tmp
+        os.makedirs(where, exist_ok=True)
+        files = []
+        for tag, lib in zip("ab", a.libs):
+            files.append(os.path.join(where, "lib_ab_%s.npz" % tag))
+            env = dict(os.environ, MVR_LIB=os.path.abspath(lib))
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", files[-1], "--cases", a.cases],
+                           env=env, check=True, timeout=300)
+        A, B = (dict(np.load(f)) for f in files)
+    bad = sorted(set(A) ^ set(B))
+    for k in sorted(set(A) & set(B)):
+        if A[k].dtype != B[k].dtype or A[k].shape != B[k].shape or A[k].tobytes() != B[k].tobytes():
+            bad.append(k)
+    written = sum(int((v != SENT).sum()) for v in A.values())
+    print("%d keys, %d bytes, %d values written: %s" % (len(A), sum(v.nbytes for v in A.values()), written,
+                                                        "all identical" if not bad else "DIFFERENT: " + ", ".join(bad)))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
