@@ -1,5 +1,6 @@
 // The covariance of a ball's points and the 3 x 3 symmetric Jacobi eigen-solver, shared by the normals (normals.hip)
-// and the ISS saliency (iss.hip).  fp64, registers only; every loop is bounded (ball_walk's, the Jacobi sweep cap).
+// and the ISS saliency (iss.hip), and the tangent-plane sums of the colour gradients (color_grad.hip).  fp64,
+// registers only; every loop is bounded (ball_walk's, the Jacobi sweep cap).
 #pragma once
 #include "common.hpp"
 #include "rindex.hpp"
@@ -75,6 +76,29 @@ __device__ __forceinline__ void ball_sums(const RIndex& ix, const double* __rest
   n = k;
   for (int e = 0; e < 3; ++e) m[e] = sm[e];
   for (int e = 0; e < 6; ++e) S[e] = sS[e];
+}
+
+// The walk of the same ball with a per-neighbour value (color_grad.hip): with e = x_j - p and u = e - (e . nv) nv its
+// part in the tangent plane of the normal nv, n points, A = sum u u^T as xx xy xz yy yz zz and h = sum u (f(j) - f0),
+// in the walk's order.  value(j) is row j's scalar, f0 the point's own (whose row adds u = 0 and a difference of 0).
+template <class F>
+__device__ __forceinline__ void ball_tangent_sums(const RIndex& ix, const double* __restrict__ xyz, int b,
+                                                  const double (&p)[3], const double (&nv)[3], double f0, double r,
+                                                  double radius, F&& value, int& n, double (&A)[6], double (&h)[3]) {
+  int k = 0;
+  double sA[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, sh[3] = {0.0, 0.0, 0.0};
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, double ex, double ey, double ez) {
+    ++k;
+    const double en = ex * nv[0] + ey * nv[1] + ez * nv[2];
+    const double ux = ex - en * nv[0], uy = ey - en * nv[1], uz = ez - en * nv[2];
+    const double df = value(t) - f0;
+    sA[0] += ux * ux; sA[1] += ux * uy; sA[2] += ux * uz;
+    sA[3] += uy * uy; sA[4] += uy * uz; sA[5] += uz * uz;
+    sh[0] += ux * df; sh[1] += uy * df; sh[2] += uz * df;
+  });
+  n = k;
+  for (int e = 0; e < 6; ++e) A[e] = sA[e];
+  for (int e = 0; e < 3; ++e) h[e] = sh[e];
 }
 
 // a = S / n - (m / n)(m / n)^T, the covariance about the ball's own mean; m becomes the mean.  n >= 1.

@@ -1,11 +1,12 @@
 // What the radius-index nearest-neighbour kernels share: the search of the nearest target point
-// (icp.hip, icp_plane.hip, icp_gicp.hip, icp_robust.hip, info.hip), the validation of a pair, and for the ICP kernels
+// (icp.hip, icp_plane.hip, icp_gicp.hip, icp_robust.hip, icp_colored.hip, info.hip), the validation of a pair, and for the ICP kernels
 // the args struct with its host-side checks, the loop with its stopping rule, trace and status bits, and the 6 x 6
 // solve with the update of T.  A kernel supplies a model: what a match adds to the sums and what lane 0 solves from
 // them.
-// The three models live here too, each with a weight policy: UnitWeight for the plain kernels, where
-// the weight is a type and nothing is generated for it, KernelWeight for icp_robust.hip's robust kernels.
-// Everything is inlined into the kernel that uses it; each of the five sources stays its own translation unit.
+// The four models live here too, each with a weight policy: UnitWeight for the plain kernels, where
+// the weight is a type and nothing is generated for it, KernelWeight for the robust kernels of icp_robust.hip and
+// icp_colored.hip.
+// Everything is inlined into the kernel that uses it; each of the six sources stays its own translation unit.
 #pragma once
 #include "common.hpp"
 #include "rindex.hpp"
@@ -140,6 +141,12 @@ struct RobustArgs : IcpArgs {
   int kernel; double kernel_k; double* w_sum;
 };
 
+// mvr_icp_refine_colored's: the intensities and their tangent-plane gradients (color_grad.hip), and the share lambda
+// of the geometric term (uniform)
+struct ColoredArgs : RobustArgs {
+  const double* intensity; const double* grad; double lambda;
+};
+
 // ----------------------------------------------------------------------------------------------------- weight policies
 // What a model multiplies a match's terms with.  The plain kernels' weight is a type: w * x is x, and neither the
 // residual nor a product is generated for it, so their code is what it was without weights.
@@ -167,6 +174,15 @@ struct KernelWeight {
       default: { const double s = r / k, u = 1.0 - s * s; return fabs(r) <= k ? u * u : 0.0; }   // Tukey
     }
   }
+};
+
+// Whether an unweighted model still reports w_sum: kCountIsWeightSum in the model (the coloured one, whose unit weights
+// sum to the count).  The models without it generate nothing for it
+template <class Model, class = void>
+struct CountIsWeightSum { static constexpr bool value = false; };
+template <class Model>
+struct CountIsWeightSum<Model, decltype((void)Model::kCountIsWeightSum)> {
+  static constexpr bool value = Model::kCountIsWeightSum;
 };
 
 // The loop of one pair, every iteration inside the one launch (mvreg.h mvr_icp_refine has the semantics).  Model:
@@ -200,7 +216,7 @@ __device__ __forceinline__ void icp_loop(const typename Model::Args& a) {
       if (a.n_corr) a.n_corr[p] = 0;
       if (a.iters) a.iters[p] = 0;
       a.status[p] = 4;
-      if constexpr (Model::kWeighted)
+      if constexpr (Model::kWeighted || CountIsWeightSum<Model>::value)
         if (a.w_sum) a.w_sum[p] = 0.0;
     }
     if (trace)
@@ -262,6 +278,8 @@ __device__ __forceinline__ void icp_loop(const typename Model::Args& a) {
     a.status[p] = status;
     if constexpr (Model::kWeighted)
       if (a.w_sum) a.w_sum[p] = v[kSums - 1];   // of the last evaluation: the returned T's, also after a failed solve
+    if constexpr (CountIsWeightSum<Model>::value)
+      if (a.w_sum) a.w_sum[p] = v[0];
   }
   if (trace)
     for (int64_t e = 2 * ((int64_t)k + 1) + tid; e < 2 * rows; e += kThreads) trace[e] = -1.0;
@@ -453,6 +471,54 @@ struct GeneralizedT : SixDofModelT<Wt> {
 #pragma unroll
     for (int f = 0; f < 6; ++f) v[23 + f] += gd[f];
     if constexpr (Base::kWeighted) v[kSums - 1] += wt;
+  }
+};
+
+// Coloured (mvreg.h mvr_icp_refine_colored; Park et al. 2017, Open3D's registration_colored_icp): per match two
+// rank-one terms on the point-to-plane layout, the geometric one a_G = [(q - c) x n, n], b_G = (q - y) . n with the
+// share lambda, and the photometric one a_I = [(q - c) x dM, dM], b_I = I_s - (I_t + d . (e - b_G n)) with dM =
+// -(d - (d . n) n) (d the target's gradient) and the share 1 - lambda.  Each has its own weight, of its residual scaled
+// by the root of its share; sum w is sum (lambda w_G + (1 - lambda) w_I), with unit weights the count.  One term is
+// added after the other, so only one a of 6 is live beside the sums
+template <class Wt>
+struct ColoredT : SixDofModelT<Wt> {
+  using Base = SixDofModelT<Wt>;
+  using Base::kSums;
+  using Args = ColoredArgs;
+  static constexpr bool kCountIsWeightSum = !Base::kWeighted;
+
+  template <class W>
+  __device__ __forceinline__ static void rank_one(double (&v)[kSums], W wt, const double (&w)[3], const double (&m)[3],
+                                                  double b) {
+    const double ja[6] = {w[1] * m[2] - w[2] * m[1], w[2] * m[0] - w[0] * m[2], w[0] * m[1] - w[1] * m[0],
+                          m[0], m[1], m[2]};
+    int h = 2;
+#pragma unroll
+    for (int f = 0; f < 6; ++f)
+#pragma unroll
+      for (int g = f; g < 6; ++g) v[h++] += (wt * ja[f]) * ja[g];
+#pragma unroll
+    for (int f = 0; f < 6; ++f) v[23 + f] += (wt * ja[f]) * b;
+  }
+
+  __device__ __forceinline__ static void accumulate(const Args& a, const double* sT, const double* sC,
+                                                    double (&v)[kSums], int64_t i, int64_t bt, const double (&q)[3],
+                                                    double d2) {
+    const double lam = a.lambda, oml = 1.0 - a.lambda;
+    const double n[3] = {a.normals[3 * bt], a.normals[3 * bt + 1], a.normals[3 * bt + 2]};
+    const double e[3] = {q[0] - a.xyz[3 * bt], q[1] - a.xyz[3 * bt + 1], q[2] - a.xyz[3 * bt + 2]};
+    const double w[3] = {q[0] - sC[0], q[1] - sC[1], q[2] - sC[2]};
+    const double bG = e[0] * n[0] + e[1] * n[1] + e[2] * n[2];
+    const auto wG = Wt::weight(a, [&] { return sqrt(lam) * bG; });
+    rank_one(v, wG * lam, w, n, bG);
+    const double d[3] = {a.grad[3 * bt], a.grad[3 * bt + 1], a.grad[3 * bt + 2]};
+    const double dn = d[0] * n[0] + d[1] * n[1] + d[2] * n[2];
+    const double dM[3] = {-(d[0] - dn * n[0]), -(d[1] - dn * n[1]), -(d[2] - dn * n[2])};
+    const double bI = a.intensity[i] - (a.intensity[bt] + (d[0] * (e[0] - bG * n[0]) + d[1] * (e[1] - bG * n[1]) +
+                                                           d[2] * (e[2] - bG * n[2])));
+    const auto wI = Wt::weight(a, [&] { return sqrt(oml) * bI; });
+    rank_one(v, wI * oml, w, dM, bI);
+    if constexpr (Base::kWeighted) v[kSums - 1] += wG * lam + wI * oml;
   }
 };
 

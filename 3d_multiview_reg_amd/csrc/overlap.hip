@@ -97,6 +97,24 @@ __global__ void centroid_kernel(const float* __restrict__ xyz, const uint64_t* _
   if (i == 0 || (int)(k[i - 1] >> (3 * OV_BITS)) != b) out_off[b] = o;   // first voxel of fragment b
 }
 
+// one thread per voxel: the fp64 mean of its points' colours, summed in input order like the centroid
+__global__ void voxel_color_kernel(const float* __restrict__ colors, const uint64_t* __restrict__ k,
+                                   const int32_t* __restrict__ sidx, const int32_t* __restrict__ head,
+                                   const int32_t* __restrict__ pos, int64_t n, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !head[i]) return;
+  double s[3] = {0.0, 0.0, 0.0};
+  int64_t j = i;
+  do {
+    const int64_t q = sidx[j];
+    for (int d = 0; d < 3; ++d) s[d] += (double)colors[3 * q + d];
+    ++j;
+  } while (j < n && k[j] == k[i]);
+  const double cnt = (double)(j - i);
+  const int64_t o = pos[i];
+  for (int d = 0; d < 3; ++d) out[3 * o + d] = s[d] / cnt;
+}
+
 __global__ void fix_offsets_kernel(int64_t* out_off, int B, const int32_t* head, const int32_t* pos, int64_t n) {
   const bool over = out_off[B] == OV_OVER_RANGE;
   out_off[B] = n > 0 ? (int64_t)pos[n - 1] + head[n - 1] : 0;
@@ -205,8 +223,10 @@ extern "C" size_t mvr_voxel_centroids_workspace_bytes(int64_t n) {
   return m * (8 + 8 + 4 + 4 + 4) + sort_bytes(n) + scan_bytes(n) + 4096 * 24 + 10 * 256;
 }
 
-extern "C" int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel,
-                                   void* ws, size_t ws_bytes, double* out_xyz, int64_t* out_off, hipStream_t s) {
+// mvr_voxel_centroids and mvr_voxel_centroids_colored: the same passes, and with colors one more kernel
+static int voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel, void* ws,
+                           size_t ws_bytes, const float* colors, double* out_xyz, int64_t* out_off, double* out_colors,
+                           hipStream_t s) {
   if (!frag_off || !out_off || B <= 0 || B > 4096 || n < 0 || n > 0x7fffffff || !(voxel > 0.0)) return MVR_EINVAL;
   if (n > 0 && (!xyz || !ws || !out_xyz || ws_bytes < mvr_voxel_centroids_workspace_bytes(n))) return MVR_EINVAL;
   if (n == 0) {   // every fragment empty: offsets all 0 (NULL point / workspace pointers allowed)
@@ -238,9 +258,23 @@ extern "C" int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, in
   if ((rc = excl_scan_i32(head, pos, n, tscan, sc, s)) != MVR_OK) return rc;
   hipLaunchKernelGGL(centroid_kernel, dim3(nb(n)), dim3(256), 0, s, xyz, kout, vout, head, pos, n, B, out_xyz,
                      out_off);
+  if (colors)
+    hipLaunchKernelGGL(voxel_color_kernel, dim3(nb(n)), dim3(256), 0, s, colors, kout, vout, head, pos, n, out_colors);
   hipLaunchKernelGGL(fix_offsets_kernel, dim3(1), dim3(1), 0, s, out_off, B, head, pos, n);
   MVR_CHECK_LAUNCH();
   return MVR_OK;
+}
+
+extern "C" int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel,
+                                   void* ws, size_t ws_bytes, double* out_xyz, int64_t* out_off, hipStream_t s) {
+  return voxel_centroids(xyz, frag_off, B, n, voxel, ws, ws_bytes, nullptr, out_xyz, out_off, nullptr, s);
+}
+
+extern "C" int mvr_voxel_centroids_colored(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel,
+                                           void* ws, size_t ws_bytes, const float* colors, double* out_xyz,
+                                           int64_t* out_off, double* out_colors, hipStream_t s) {
+  if (n > 0 && (!colors || !out_colors)) return MVR_EINVAL;
+  return voxel_centroids(xyz, frag_off, B, n, voxel, ws, ws_bytes, colors, out_xyz, out_off, out_colors, s);
 }
 
 extern "C" size_t mvr_radius_index_bytes(int64_t M) { return index_bytes(M) + build_scratch_bytes(M); }

@@ -105,6 +105,8 @@ _SIGS = {
                             c_int, c_float, c_vp, c_vp, c_vp]),
     "mvr_voxel_centroids_workspace_bytes": (c_size, [c_i64]),
     "mvr_voxel_centroids": (c_int, [c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_size, c_vp, c_vp, c_vp]),
+    "mvr_voxel_centroids_colored": (c_int, [c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_size, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp]),
     "mvr_radius_index_bytes": (c_size, [c_i64]),
     "mvr_radius_index_build": (c_int, [c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_size, c_vp]),
     "mvr_radius_overlap_count": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64,
@@ -124,6 +126,12 @@ _SIGS = {
                                       c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_int,
                                       ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp]),
+    "mvr_color_gradient": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double,
+                                   ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
+    "mvr_icp_refine_colored": (c_int, [c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp,
+                                       c_vp, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_int,
+                                       ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp]),
     "mvr_pair_information": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_int,
                                      ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mvr_compute_fpfh_workspace_bytes": (c_size, [c_i64]),

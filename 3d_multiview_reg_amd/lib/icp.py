@@ -1,15 +1,18 @@
 """Fine registration: batched ICP on the fragments' own points, point-to-point (csrc/icp.hip mvr_icp_refine,
 DESIGN.md 4.19), point-to-plane on normals (csrc/icp_plane.hip mvr_icp_refine_plane) or generalized,
 plane-to-plane, on both fragments' normals (csrc/icp_gicp.hip mvr_icp_refine_generalized); the
-semantics are in include/mvreg.h.  Each of the three takes a robust kernel (`kernel`, `kernel_k`: csrc/icp_robust.hip
-mvr_icp_refine_robust), which weighs every correspondence by its residual in the solve.
+semantics are in include/mvreg.h; coloured ICP on both the geometry and the fragments' colours is a fourth
+(csrc/icp_colored.hip mvr_icp_refine_colored).  Each of them takes a robust kernel (`kernel`,
+`kernel_k`: csrc/icp_robust.hip mvr_icp_refine_robust), which weighs every correspondence by its
+residual in the solve.
 
 The reference stops at the coarse estimate (Procrustes or RANSAC over the sampled correspondences); its users
 follow it with Open3D's `registration_icp`.  `icp_refine` does that for every pair of a scene in one launch, on the
 radius index a `FragmentOverlap` already holds; `icp_pair` keeps the one-pair shape of `registration_icp`.
-`gicp_refine` and `gicp_pair` are the same two shapes for `registration_generalized_icp`.  Restated from the maths
-and pinned to tests/icp_oracle.py, tests/icp_plane_oracle.py, tests/gicp_oracle.py and tests/icp_robust_oracle.py:
-Open3D parity is unpinned.
+`gicp_refine` and `gicp_pair` are the same two shapes for `registration_generalized_icp`, `colored_icp_refine` and
+`colored_icp_pair` for `registration_colored_icp`.  Restated from the maths and pinned to tests/icp_oracle.py,
+tests/icp_plane_oracle.py, tests/gicp_oracle.py, tests/icp_robust_oracle.py and tests/colored_icp_oracle.py: Open3D
+parity is unpinned.
 
 Convention: T maps source coordinates into the target's frame, x_target ~ R x_source + t (rot_est / trans_est of
 filter_correspondences, the input of lib.multiview.synchronize) — the inverse of the `trans` of
@@ -129,9 +132,10 @@ def _refine(name, fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse,
     return _run(name, fo, pairs, T_init, "T_init", max_dist, needs_normals, call, normals_for)
 
 
-def _pair_overlap(name, src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, normals):
-    """The shape checks of icp_pair and gicp_pair, then the two-fragment FragmentOverlap (with normals over
-    normal_radius, None: max_dist, if asked for) and T_init with the leading [1]."""
+def _pair_overlap(name, src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, normals, colors=None):
+    """The shape checks of icp_pair, gicp_pair and colored_icp_pair, then the two-fragment FragmentOverlap (with
+    normals over normal_radius, None: max_dist, if asked for; with colors, a pair of [n,3] arrays, also the colour
+    gradients over it) and T_init with the leading [1]."""
     from lib.overlap import FragmentOverlap
     if normal_radius is not None and not normal_radius > 0.0:
         raise ValueError("%s: normal_radius must be positive" % name)
@@ -146,12 +150,15 @@ def _pair_overlap(name, src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_r
         raise ValueError("%s: T_init must be a float [4,4] or [3,4]" % name)
     nr = max_dist if normal_radius is None else normal_radius
     cell = max(max_dist, nr) if normals else max_dist    # the index's cells cover the search ball and the normals'
+    with_colors = {} if colors is None else {"colors": colors}
     if voxel_size is None:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell)
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "3DMatch", radius=cell, **with_colors)
     else:
-        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell)
+        fo = FragmentOverlap([src_xyz, tgt_xyz], "FCGF", voxel_size, radius=cell, **with_colors)
     if normals:
         fo.estimate_normals(nr)
+    if colors is not None:
+        fo.compute_color_gradients(nr)
     return fo, (T_init[None] if torch.is_tensor(T_init) else np.asarray(T_init)[None])
 
 
@@ -284,4 +291,91 @@ def gicp_pair(src_xyz, tgt_xyz, T_init, max_dist=0.05, voxel_size=None, normal_r
     _check_kernel("gicp_pair", kw.get("kernel"), kw.get("kernel_k"), kw.get("return_weight_sum", False))
     fo, T0 = _pair_overlap("gicp_pair", src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, True)
     out = gicp_refine(fo, [[0, 1]], T0, max_dist, epsilon=epsilon, **kw)
+    return {k: v[0] for k, v in out.items()}
+
+
+def _check_lambda(name, lambda_geometric):
+    if not 0.0 <= lambda_geometric <= 1.0:
+        raise ValueError("%s: lambda_geometric must lie in [0, 1]" % name)
+
+
+def _check_colored(name, fo):
+    """the per-point inputs of the coloured loop: fp64, on the device, in the row order of fo.xyz; what is missing is
+    named (the normals are looked at again by _run)"""
+    for what, hint in (("normals", "fo.estimate_normals()"), ("intensity", "fo.compute_color_gradients()"),
+                       ("color_grad", "fo.compute_color_gradients()")):
+        x = getattr(fo, what, None)
+        if x is None:
+            raise ValueError("%s: needs fo.%s (call %s)" % (name, what, hint))
+        shape = (fo.M,) if what == "intensity" else (fo.M, 3)
+        if not torch.is_tensor(x) or tuple(x.shape) != shape or x.dtype != torch.float64 or \
+                x.device != fo.xyz.device or not x.is_contiguous():
+            raise ValueError("%s: fo.%s must be a contiguous fp64 %s tensor on the device of fo.xyz"
+                             % (name, what, list(shape)))
+
+
+def colored_icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6,
+                       lambda_geometric=0.968, kernel=None, kernel_k=None, return_trace=False,
+                       return_weight_sum=False):
+    """Coloured ICP on every pair of `fo`: icp_refine's arguments, conventions, stopping rule and dict, with the solve
+    of Park, Zhou and Koltun's coloured ICP (Open3D's registration_colored_icp; parity unpinned).
+
+    Every correspondence adds the point-to-plane term with the share lambda_geometric and, with the share
+    1 - lambda_geometric, a photometric term: the source point's intensity against the target's intensity and its
+    gradient in the tangent plane.  Where the geometry leaves a motion free (in the plane of a wall, a floor, a table
+    top) the colours decide it.  Needs fo.normals (from fo.estimate_normals() or assigned by the caller; taken as
+    given, their sign does not matter) and fo.intensity and fo.color_grad (from fo.compute_color_gradients(), or
+    assigned by the caller: fp64 [M] and [M,3] on the device).  lambda_geometric in [0, 1]; 1 is the point-to-plane
+    solve.  status bit STATUS_DEGENERATE as for 'point_to_plane'.  kernel, kernel_k: as icp_refine's, applied to each
+    of the two residuals scaled by the root of its share (metres for the geometric one, intensity for the photometric
+    one); None and 'l2' are the same launch.  return_weight_sum adds fp64 w_sum [P], the sum of lambda_geometric w_G +
+    (1 - lambda_geometric) w_I at the returned T (without a kernel: n_corr)."""
+    max_dist = float(fo.r if max_dist is None else max_dist)
+    _check_settings("colored_icp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
+    _check_lambda("colored_icp_refine", float(lambda_geometric))
+    robust = _check_kernel("colored_icp_refine", kernel, kernel_k, return_weight_sum and kernel is not None)
+    kernel_id, k = (0, 0.0) if robust is None else robust
+
+    if max_dist <= fo.r:       # beyond it _run raises
+        _check_colored("colored_icp_refine", fo)
+
+    def call(P, ij, T0):
+        dev = fo.device
+        T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
+        fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
+        n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+        trace = torch.empty(P, int(max_iters) + 1, 2, dtype=torch.float64, device=dev) if return_trace else None
+        w_sum = torch.empty(P, dtype=torch.float64, device=dev) if return_weight_sum else None
+        N.check(N.lib().mvr_icp_refine_colored(
+            N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals), N.ptr(fo.intensity),
+            N.ptr(fo.color_grad), N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(ij), N.ptr(T0), P, max_dist,
+            float(lambda_geometric), kernel_id, k, int(max_iters), float(tol_fitness), float(tol_rmse), N.ptr(T),
+            N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.ptr(w_sum),
+            N.stream()), "mvr_icp_refine_colored")
+        T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
+        T4[:, :3], T4[:, 3, 3] = T, 1.0
+        out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
+        if return_trace:
+            out["trace"] = trace
+        if return_weight_sum:
+            out["w_sum"] = w_sum
+        return out
+    return _run("colored_icp_refine", fo, pairs, T_init, "T_init", max_dist, True, call)
+
+
+def colored_icp_pair(src_xyz, src_colors, tgt_xyz, tgt_colors, T_init, max_dist=0.05, voxel_size=None,
+                     normal_radius=None, lambda_geometric=0.968, **kw):
+    """One pair in the shape of Open3D's registration_colored_icp(source, target, max_correspondence_distance, init):
+    icp_pair's arguments plus the two clouds' colours [n,3] / [m,3] (float in [0, 1] or uint8).  The normals and the
+    colour gradients of both clouds are estimated here over normal_radius (None: max_dist) on an index of cell
+    max(max_dist, normal_radius).  **kw: max_iters, tol_fitness, tol_rmse, return_trace, kernel, kernel_k,
+    return_weight_sum of colored_icp_refine.  Returns colored_icp_refine's dict without the leading [P]."""
+    _check_settings("colored_icp_pair", float(max_dist), kw.get("max_iters", 30), kw.get("tol_fitness", 0.0),
+                    kw.get("tol_rmse", 0.0))
+    _check_lambda("colored_icp_pair", float(lambda_geometric))
+    _check_kernel("colored_icp_pair", kw.get("kernel"), kw.get("kernel_k"),
+                  kw.get("return_weight_sum", False) and kw.get("kernel") is not None)
+    fo, T0 = _pair_overlap("colored_icp_pair", src_xyz, tgt_xyz, T_init, max_dist, voxel_size, normal_radius, True,
+                           colors=[src_colors, tgt_colors])
+    out = colored_icp_refine(fo, [[0, 1]], T0, max_dist, lambda_geometric=lambda_geometric, **kw)
     return {k: v[0] for k, v in out.items()}

@@ -397,10 +397,10 @@ def fuse_scene(fo, R, t, voxel_size, member=None, min_frags=1, min_points=1, nor
 
 
 OVERLAP_THRESHOLDS = {"3d_match": 0.3, "redwood": 0.23}   # scripts/benchmark_pairwise_registration.py --dataset
-ICP_METHODS = ("point_to_point", "point_to_plane", "generalized")
+ICP_METHODS = ("point_to_point", "point_to_plane", "generalized", "colored")
 
 
-def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
+def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints, colors=None, icp_lambda_geometric=0.968):
     """register_scene's checks that need no device -> (pairs [P,2], init [P,4,4] or None, viewpoints [n,3])"""
     if n < 2:
         raise ValueError("register_scene: needs at least two fragments")
@@ -410,6 +410,12 @@ def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints):
         raise ValueError("register_scene: voxel_size must be positive and finite")
     if method not in ICP_METHODS:
         raise ValueError("register_scene: method must be one of %s, not %r" % (", ".join(ICP_METHODS), method))
+    if method == "colored" and colors is None:
+        raise ValueError("register_scene: method 'colored' needs colors, one [n_b,3] array per fragment")
+    if colors is not None and len(colors) != n:
+        raise ValueError("register_scene: colors must hold one array per fragment (%d, not %d)" % (n, len(colors)))
+    if not 0.0 <= float(icp_lambda_geometric) <= 1.0:
+        raise ValueError("register_scene: icp_lambda_geometric must lie in [0, 1]")
     if dataset not in OVERLAP_THRESHOLDS:
         raise ValueError("register_scene: dataset must be one of %s, not %r"
                          % (", ".join(sorted(OVERLAP_THRESHOLDS)), dataset))
@@ -488,11 +494,13 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
                    icp_max_dist=None, icp_iters=30, gicp_epsilon=1e-3, anchor=0, refine_iters=20, fuse_voxel=None,
                    min_frags=1, min_points=1, ransac_checkers=False, line_process=False,
                    preference_loop_closure=1.0, denoise=None, coarse="ransac", keypoints=None, icp_kernel=None,
-                   icp_kernel_k=None):
+                   icp_kernel_k=None, colors=None, icp_lambda_geometric=0.968):
     """Fragments in, registered scene out, without a pretrained network: the chain of the stages this library has,
     composed (nothing is computed here).  xyz_list: n point arrays [n_b,3] in their own frames.
       1. lib.overlap.FragmentOverlap: voxel centroids of size voxel_size on an index of radius 3 voxel_size
-         (downsample False: the points as given on the same index);
+         (downsample False: the points as given on the same index); colors (None: none): one [n_b,3] array per
+         fragment, float in [0, 1] or uint8, carried to fo.colors through every stage (a voxel's colour is the mean of
+         its points');
       1b. denoise (None: nothing, the chain and the result as without it): {"method": "statistical", "nb_neighbors":
          20, "std_ratio": 2.0} or {"method": "radius", "nb_points": 16, "radius": None} (options may be left out) —
          fo.statistical_outliers / fo.radius_outliers per fragment, then fo = fo.select(keep): every later stage,
@@ -509,8 +517,10 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
          (init [P,4,4], x_j ~ T x_i for the pairs i < j in that order, replaces 3 and 4);
       5. the overlap gate of the pairwise benchmark: a pair is kept when FragmentOverlap.ratios >= overlap_threshold
          (None: the benchmark's value for `dataset`, 0.3 for '3d_match', 0.23 for 'redwood');
-      6. lib.icp.icp_refine (method 'point_to_point' / 'point_to_plane') or gicp_refine ('generalized') on the kept
-         pairs; icp_kernel (None: every correspondence weighs 1, the chain and the result as without it): one of
+      6. lib.icp.icp_refine (method 'point_to_point' / 'point_to_plane'), gicp_refine ('generalized') or
+         colored_icp_refine ('colored': needs colors; fo.compute_color_gradients(normal_radius) runs after step 2,
+         the share of the geometric term is icp_lambda_geometric) on the kept pairs; icp_kernel (None: every
+         correspondence weighs 1, the chain and the result as without it): one of
          lib.icp.ROBUST_KERNELS with its scale icp_kernel_k, None: voxel_size, the sampling scale of the centroids
          (a documented default, not a tuned value; 'gm' takes a squared length, so give it one);  7. lib.icp.information_matrix;  8. synchronize(irls_iters=5);  9. optimize_pose_graph with the
          IRLS weights (line_process: with Open3D's line process and edge pruning, every kept pair an uncertain edge,
@@ -525,14 +535,15 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     points each fragment lost); with keypoints also keypoints: rows [K] (rows of fo.xyz, ascending) and off [n+1]
     (numpy int64)."""
     from lib.fpfh import register_fgr, register_fpfh
-    from lib.icp import _check_kernel, gicp_refine, icp_refine, information_matrix
+    from lib.icp import _check_kernel, colored_icp_refine, gicp_refine, icp_refine, information_matrix
     from lib.overlap import FragmentOverlap
     n = len(xyz_list)
     if coarse not in COARSE_METHODS:
         raise ValueError("register_scene: coarse must be one of %s, not %r" % (", ".join(COARSE_METHODS), coarse))
     if coarse == "fgr" and ransac_checkers is not False:
         raise ValueError("register_scene: ransac_checkers belongs to coarse='ransac', not to coarse='fgr'")
-    pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints)
+    pairs, init, viewpoints = _scene_arguments(n, voxel_size, method, dataset, init, viewpoints, colors,
+                                               icp_lambda_geometric)
     if icp_kernel is not None and icp_kernel_k is None:
         icp_kernel_k = float(voxel_size)
     _check_kernel("register_scene", icp_kernel, icp_kernel_k)
@@ -541,10 +552,11 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     keypoints = _keypoints_arguments(keypoints, 3.0 * float(voxel_size), init)
     threshold = OVERLAP_THRESHOLDS[dataset] if overlap_threshold is None else float(overlap_threshold)
     P = len(pairs)
+    with_colors = {} if colors is None else {"colors": colors}
     if downsample:
-        fo = FragmentOverlap(xyz_list, "FCGF", voxel_size)
+        fo = FragmentOverlap(xyz_list, "FCGF", voxel_size, **with_colors)
     else:
-        fo = FragmentOverlap(xyz_list, "3DMatch", radius=3.0 * float(voxel_size))
+        fo = FragmentOverlap(xyz_list, "3DMatch", radius=3.0 * float(voxel_size), **with_colors)
     denoised = None
     if denoise is not None:
         if denoise["method"] == "statistical":
@@ -555,6 +567,8 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
         fo = fo.select(keep)
         denoised = {"keep": keep.cpu().numpy(), "removed": (sizes - np.diff(fo.off)).astype(np.int64)}
     fo.estimate_normals(normal_radius, viewpoints)
+    if method == "colored":
+        fo.compute_color_gradients(normal_radius)
     if init is None:
         fo.compute_fpfh(fpfh_radius)
         kp_args = {}
@@ -574,6 +588,9 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     if method == "generalized":
         ref = gicp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, epsilon=gicp_epsilon,
                           **robust)
+    elif method == "colored":
+        ref = colored_icp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters,
+                                 lambda_geometric=icp_lambda_geometric, **robust)
     else:
         ref = icp_refine(fo, kp, T_coarse[kept], max_dist=icp_max_dist, max_iters=icp_iters, method=method, **robust)
     Tk = np.asarray(ref["T"], dtype=np.float64).reshape(-1, 4, 4)

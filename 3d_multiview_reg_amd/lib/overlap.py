@@ -88,6 +88,27 @@ def _iss_arguments(salient_radius, non_max_radius, gamma_21, gamma_32, min_neigh
     return radii[0], radii[1], gammas[0], gammas[1], int(min_neighbors), float(min_ratio)
 
 
+def _color_rows(colors, n_raw):
+    """FragmentOverlap's check of `colors` that needs no device -> a list of fp64 [n_b,3] host tensors in [0, 1]:
+    uint8 values are divided by 255, float values taken as they are"""
+    if len(colors) != len(n_raw):
+        raise ValueError("FragmentOverlap: colors must hold one array per fragment (%d, not %d)"
+                         % (len(n_raw), len(colors)))
+    out = []
+    for b, c in enumerate(colors):
+        c = torch.as_tensor(np.asarray(c) if not torch.is_tensor(c) else c).cpu()
+        if c.dim() != 2 or tuple(c.shape) != (int(n_raw[b]), 3):
+            raise ValueError("FragmentOverlap: colors[%d] must be [%d,3], one row per point, not %s"
+                             % (b, int(n_raw[b]), list(c.shape)))
+        if c.dtype == torch.uint8:
+            c = c.to(torch.float64) / 255.0
+        elif not c.is_floating_point():
+            raise ValueError("FragmentOverlap: colors must be uint8 or float, not %s"
+                             % str(c.dtype).replace("torch.", ""))
+        out.append(c.to(torch.float64))
+    return out
+
+
 def _keep_mask(keep, M):
     """select's check of its mask -> a bool tensor [M] (on whatever device keep was)"""
     keep = torch.as_tensor(np.asarray(keep) if not torch.is_tensor(keep) else keep)
@@ -100,9 +121,12 @@ def _keep_mask(keep, M):
 class FragmentOverlap(object):
     """Downsampled (method 'FCGF') or raw ('3DMatch') fragments of a scene with a radius index on the
     GPU.  xyz_list: list of [n_b, 3] arrays / tensors (any float dtype).  radius: the index's cell size and the
-    match radius instead of the method's (lib.icp refines on an index whose cells cover its search ball)."""
+    match radius instead of the method's (lib.icp refines on an index whose cells cover its search ball).
+    colors: None, or a list of [n_b, 3] arrays, float in [0, 1] or uint8 (divided by 255): fo.colors is then fp64
+    [M,3] on the device in the row order of fo.xyz, for 'FCGF' the mean of each voxel's colours (Open3D's
+    voxel_down_sample; the colours pass through float32 there, as the points do)."""
 
-    def __init__(self, xyz_list, method="FCGF", voxel_size=0.025, device=None, radius=None):
+    def __init__(self, xyz_list, method="FCGF", voxel_size=0.025, device=None, radius=None, colors=None):
         N.require_hip()
         dev = device or torch.device("cuda", torch.cuda.current_device())
         self.method, self.voxel_size, self.r = method, float(voxel_size), _radius(method, voxel_size)
@@ -113,6 +137,9 @@ class FragmentOverlap(object):
         pts = [torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x) for x in xyz_list]
         n_raw = np.array([int(p.shape[0]) for p in pts], dtype=np.int64)
         off_raw = np.concatenate([[0], np.cumsum(n_raw)]).astype(np.int64)
+        if colors is not None:
+            colors = _color_rows(colors, n_raw)
+        self.colors = None
         if method == "FCGF":
             xyz = torch.cat([p.reshape(-1, 3).to(dev, torch.float32) for p in pts]).contiguous()
             off_dev = torch.from_numpy(off_raw).to(dev)
@@ -121,17 +148,28 @@ class FragmentOverlap(object):
             ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
             cent = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)
             off = torch.empty(B + 1, dtype=torch.int64, device=dev)
-            N.check(L.mvr_voxel_centroids(N.ptr(xyz), N.ptr(off_dev), B, n, self.voxel_size, N.ptr(ws), ws_b,
-                                          N.ptr(cent), N.ptr(off), N.stream()), "mvr_voxel_centroids")
+            if colors is None:
+                N.check(L.mvr_voxel_centroids(N.ptr(xyz), N.ptr(off_dev), B, n, self.voxel_size, N.ptr(ws), ws_b,
+                                              N.ptr(cent), N.ptr(off), N.stream()), "mvr_voxel_centroids")
+            else:
+                rgb = torch.cat([c.to(dev, torch.float32) for c in colors]).contiguous()
+                mean = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)
+                N.check(L.mvr_voxel_centroids_colored(N.ptr(xyz), N.ptr(off_dev), B, n, self.voxel_size, N.ptr(ws),
+                                                      ws_b, N.ptr(rgb), N.ptr(cent), N.ptr(off), N.ptr(mean),
+                                                      N.stream()), "mvr_voxel_centroids_colored")
             self.off = off.cpu().numpy()
             if self.off[-1] < 0:    # set on the device by mvr_voxel_centroids: no synchronisation beyond this copy
                 raise ValueError("FragmentOverlap: a fragment spans more than %d voxels of size %g along an axis "
                                  "(voxel indices are 16-bit, so an extent of at most %g); use a larger voxel_size"
                                  % (MAX_VOXELS_PER_AXIS, self.voxel_size, MAX_VOXELS_PER_AXIS * self.voxel_size))
             self.xyz = cent[:int(self.off[-1])].contiguous()
+            if colors is not None:
+                self.colors = mean[:int(self.off[-1])].contiguous()
         else:
             self.xyz = torch.cat([p.reshape(-1, 3).to(dev, torch.float64) for p in pts]).contiguous()
             self.off = off_raw
+            if colors is not None:
+                self.colors = torch.cat([c.to(dev) for c in colors]).reshape(-1, 3).contiguous()
         self.B, self.M = B, int(self.off[-1])
         self.off_dev = torch.from_numpy(self.off).to(dev)
         self.max_points = int(np.max(np.diff(self.off))) if B else 0
@@ -142,6 +180,7 @@ class FragmentOverlap(object):
         self.device = dev
         self.normals = self.n_nbr = None   # set by estimate_normals, or normals assigned by the caller
         self.fpfh = None                   # set by compute_fpfh
+        self.intensity = self.color_grad = self.color_n_nbr = None   # set by compute_color_gradients
 
     def estimate_normals(self, radius=None, viewpoints=None):
         """Per-point normals of every fragment (csrc/normals.hip mvr_estimate_normals: Open3D's estimate_normals with
@@ -194,6 +233,38 @@ class FragmentOverlap(object):
                                    ws_b, N.stream()), "mvr_compute_fpfh")
         self.fpfh = fpfh
         return fpfh
+
+    def compute_color_gradients(self, radius=None):
+        """Per-point intensity and its gradient in the tangent plane (csrc/color_grad.hip mvr_color_gradient: what
+        Open3D's registration_colored_icp prepares on its target, restated; the semantics are in include/mvreg.h) over
+        the neighbours of the same fragment closer than `radius` (None: fo.r; at most fo.r).  Needs fo.colors (the
+        constructor's `colors`) and fo.normals (from estimate_normals or assigned by the caller; their sign does not
+        matter).  Stores fo.intensity (fp64 [M]), fo.color_grad (fp64 [M,3]) and fo.color_n_nbr (int32 [M], the
+        neighbour counts), device, the row order of fo.xyz, and returns them as a dict of intensity, grad and
+        n_nbr."""
+        radius = float(self.r if radius is None else radius)
+        if not 0.0 < radius <= self.r:
+            raise ValueError("compute_color_gradients: radius %g must lie in (0, %g], the index's cell size (build "
+                             "the FragmentOverlap with radius >= it)" % (radius, self.r))
+        if self.colors is None:
+            raise ValueError("compute_color_gradients: needs fo.colors (build the FragmentOverlap with colors=...)")
+        nrm = self.normals
+        if nrm is None:
+            raise ValueError("compute_color_gradients: needs fo.normals (call fo.estimate_normals())")
+        for what, x in (("normals", nrm), ("colors", self.colors)):
+            if not torch.is_tensor(x) or tuple(x.shape) != (self.M, 3) or x.dtype != torch.float64 or \
+                    x.device != self.xyz.device or not x.is_contiguous():
+                raise ValueError("compute_color_gradients: fo.%s must be a contiguous fp64 [%d,3] tensor on the "
+                                 "device of fo.xyz" % (what, self.M))
+        intensity = torch.empty(self.M, dtype=torch.float64, device=self.device)
+        grad = torch.empty(self.M, 3, dtype=torch.float64, device=self.device)
+        n_nbr = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        N.check(N.lib().mvr_color_gradient(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(nrm),
+                                           N.ptr(self.colors), N.ptr(self.off_dev), self.B, self.M, self.r, radius,
+                                           N.ptr(intensity), N.ptr(grad), N.ptr(n_nbr), N.stream()),
+                "mvr_color_gradient")
+        self.intensity, self.color_grad, self.color_n_nbr = intensity, grad, n_nbr
+        return {"intensity": intensity, "grad": grad, "n_nbr": n_nbr}
 
     def knn(self, k):
         """The k nearest points of every point within its own fragment, the point itself among them (csrc/knn_self.hip
@@ -270,8 +341,9 @@ class FragmentOverlap(object):
 
     def select(self, keep):
         """A new FragmentOverlap over the rows with keep[i] (bool / uint8 [M], array or tensor), in their order: the
-        same method, voxel_size, r and device, `off` recomputed, the index rebuilt (no voxel pass), normals, n_nbr and
-        fpfh None since the neighbourhoods changed.  parent_rows (int64 [M'], device) maps its rows to this object's.
+        same method, voxel_size, r and device, `off` recomputed, the index rebuilt (no voxel pass), normals, n_nbr,
+        fpfh and the colour gradients None since the neighbourhoods changed; colors are the kept rows' (they do not
+        depend on neighbourhoods).  parent_rows (int64 [M'], device) maps its rows to this object's.
         A fragment may become empty."""
         keep = _keep_mask(keep, self.M).to(self.device)
         rows = torch.nonzero(keep).reshape(-1)
@@ -290,6 +362,8 @@ class FragmentOverlap(object):
         N.check(L.mvr_radius_index_build(N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(fo.index), ib,
                                          N.stream()), "mvr_radius_index_build")
         fo.normals = fo.n_nbr = fo.fpfh = None
+        fo.colors = None if self.colors is None else self.colors[rows].contiguous()
+        fo.intensity = fo.color_grad = fo.color_n_nbr = None
         fo.parent_rows = rows
         return fo
 

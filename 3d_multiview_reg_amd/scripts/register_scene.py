@@ -16,9 +16,11 @@ before anything else uses them; the points removed per fragment are printed.
 are detected on each fragment and the FPFH matching runs on them alone; the keypoints per fragment are printed.
 --icp_kernel huber|cauchy|gm|tukey|l2[:K]: the ICP stage weighs every correspondence by a robust kernel of scale K
 (K defaults to the voxel size; lib.icp.ROBUST_KERNELS); the kernel and its scale are printed.
+--icp_method colored: coloured ICP (Open3D's registration_colored_icp) on the red / green / blue properties of the
+fragments' PLY files, which must all have them; --icp_lambda_geometric is the share of the geometric term.
 
 usage: python -m scripts.register_scene --fragments F0.ply F1.ply ... --out DIR [--voxel_size 0.025]
-           [--icp_method point_to_point] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
+           [--icp_method point_to_point | colored [--icp_lambda_geometric 0.968]] [--init traj.txt] [--dataset 3d_match] [--min_frags 1] [--seed 0]
            [--checkers | --coarse fgr] [--line_process [--preference_loop_closure 1.0]] [--denoise statistical:20:2.0]
            [--keypoints iss[:SALIENT:NONMAX]] [--icp_kernel tukey[:K]]
 """
@@ -32,11 +34,11 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
-from lib.ply import read_ply_xyz, write_ply  # noqa: E402
+from lib.ply import read_ply_colors, read_ply_xyz, write_ply  # noqa: E402
 from lib.utils import ensure_dir, read_trajectory, write_trajectory  # noqa: E402
 from scripts.multiview_sync import write_poses  # noqa: E402
 
-ICP_METHODS = ("point_to_point", "point_to_plane", "generalized")   # lib.multiview.ICP_METHODS
+ICP_METHODS = ("point_to_point", "point_to_plane", "generalized", "colored")   # lib.multiview.ICP_METHODS
 DATASETS = ("3d_match", "redwood")                                  # lib.multiview.OVERLAP_THRESHOLDS
 COARSE_METHODS = ("ransac", "fgr")                                  # lib.multiview.COARSE_METHODS
 ROBUST_KERNELS = ("l2", "huber", "cauchy", "gm", "tukey")           # lib.icp.ROBUST_KERNELS
@@ -101,12 +103,25 @@ def parse_icp_kernel(text):
     return parts[0], k
 
 
+def read_colored_fragments(paths):
+    """the fragments' points and colours for --icp_method colored (ValueError naming the files without red / green /
+    blue) -> (xyz list, colors list)"""
+    both = [read_ply_colors(f) for f in paths]
+    bare = [f for f, (_, c) in zip(paths, both) if c is None]
+    if bare:
+        raise ValueError("--icp_method colored needs red, green and blue vertex properties; none in %s"
+                         % ", ".join(bare))
+    return [x for x, _ in both], [c for _, c in both]
+
+
 def parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--fragments", required=True, nargs="+", help="the fragments' PLY files (at least two)")
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--voxel_size", type=float, default=0.025, help="voxel size of the centroids and of the scene")
     ap.add_argument("--icp_method", default="point_to_point", choices=ICP_METHODS)
+    ap.add_argument("--icp_lambda_geometric", type=float, default=0.968,
+                    help="--icp_method colored: the share of the geometric term, in [0, 1] (Open3D's lambda_geometric)")
     ap.add_argument("--init", default=None, help="traj.txt with an estimate for every pair i < j instead of FPFH")
     ap.add_argument("--dataset", default="3d_match", choices=DATASETS,
                     help="the overlap gate's threshold, as the pairwise benchmark picks it: 0.3 / 0.23")
@@ -146,6 +161,8 @@ def check_args(ap, a):
         ap.error("--anchor outside the fragments")
     if a.coarse == "fgr" and a.checkers:
         ap.error("--checkers belongs to --coarse ransac")
+    if not 0.0 <= a.icp_lambda_geometric <= 1.0:
+        ap.error("--icp_lambda_geometric must lie in [0, 1]")
     if not a.preference_loop_closure > 0.0:
         ap.error("--preference_loop_closure must be positive")
     if a.denoise is not None:
@@ -172,10 +189,16 @@ def main(argv=None):
     from lib.multiview import register_scene
     ap = parser()
     a = check_args(ap, ap.parse_args(argv))
-    frags = [read_ply_xyz(f) for f in a.fragments]
+    colors = None
+    if a.icp_method == "colored":
+        frags, colors = read_colored_fragments(a.fragments)
+    else:
+        frags = [read_ply_xyz(f) for f in a.fragments]
     init = None if a.init is None else read_init(a.init, len(frags))
     res = register_scene(frags, a.voxel_size, method=a.icp_method, init=init, dataset=a.dataset, seed=a.seed,
                          anchor=a.anchor, min_frags=a.min_frags, ransac_checkers=a.checkers,
+                         **({} if colors is None else dict(colors=colors,
+                                                           icp_lambda_geometric=a.icp_lambda_geometric)),
                          **({} if a.coarse == "ransac" else dict(coarse=a.coarse)),
                          **({} if not a.line_process else dict(line_process=True,
                                                                preference_loop_closure=a.preference_loop_closure)),

@@ -385,11 +385,19 @@ int mvr_xs_to_channels(const float* xs, int64_t xs_pstride, int64_t xs_nstride, 
 size_t mvr_voxel_centroids_workspace_bytes(int64_t n);
 int mvr_voxel_centroids(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel, void* workspace,
                         size_t workspace_bytes, double* out_xyz, int64_t* out_off, mvr_stream_t stream);
+/* mvr_voxel_centroids with colours: colors float32 [n,3] in the row order of xyz, out_colors fp64 [n,3] capacity in
+ * the row order of out_xyz: the fp64 mean of the voxel's colours, summed in input order (what Open3D's
+ * voxel_down_sample does with colours).  The same passes: out_xyz and out_off are bit-identical to
+ * mvr_voxel_centroids', and the workspace is mvr_voxel_centroids_workspace_bytes(n).  With n > 0 colors and
+ * out_colors must not be NULL. */
+int mvr_voxel_centroids_colored(const float* xyz, const int64_t* frag_off, int B, int64_t n, double voxel,
+                                void* workspace, size_t workspace_bytes, const float* colors, double* out_xyz,
+                                int64_t* out_off, double* out_colors, mvr_stream_t stream);
 /* Radius index over fp64 points [M,3] in fragments off [B+1] (device): points sorted by (fragment, cell of
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
  * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane,
- * mvr_icp_refine_generalized, mvr_compute_fpfh, mvr_knn_self, mvr_radius_count, mvr_iss_saliency and mvr_radius_nms
- * calls on the same points.
+ * mvr_icp_refine_generalized, mvr_compute_fpfh, mvr_knn_self, mvr_radius_count, mvr_iss_saliency, mvr_radius_nms,
+ * mvr_color_gradient and mvr_icp_refine_colored calls on the same points.
  * B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
@@ -578,6 +586,62 @@ int mvr_icp_refine_robust(const void* index, size_t index_bytes, const double* x
                           int max_iters, double tol_fitness, double tol_rmse, double* T, double* fitness, double* rmse,
                           int32_t* n_corr, int32_t* iters, int32_t* status, double* trace, double* w_sum,
                           mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Per-point intensity and its tangent-plane gradient on a radius index (csrc/color_grad.hip): what
+ * Open3D's registration_colored_icp prepares on its target (InitializePointCloudForColoredICP), restated from the
+ * maths; Open3D parity is unpinned.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`.
+ *   normals [M,3] (taken as given, not renormalised; their sign does not matter), colors fp64 [M,3] in the row order
+ *   of xyz.
+ *   intensity[i] = I_i = (c0 + c1 + c2) / 3.0, evaluated in that order.
+ *   The neighbours of point i are the points of its own fragment with sqrt(ex*ex + ey*ey + ez*ez) < radius (strict),
+ *   e = x_j - x_i; the point itself is one of them.  n_nbr[i] = their number (n_nbr may be NULL).  Fewer than 4: the
+ *   gradient is 0.  Otherwise, with n the normal of i and u = e - (e . n) n over the neighbours in the index's walk
+ *   order:  A = sum u u^T + (n_nbr - 1)^2 n n^T,  h = sum u (I_j - I_i);  grad[i] = d with A d = h by 3 x 3 Cholesky
+ *   (the normal equations of Open3D's rows u_j . d = I_j - I_i and (n_nbr - 1) n . d = 0).  A pivot that fails
+ *   pivot > 1e-12 max_i A_ii (a NaN fails it too) gives gradient 0, and so does a solution that is not finite (a NaN
+ *   or infinite colour in the ball): the gradient is always finite.
+ *   intensity [M], grad [M,3] and n_nbr [M] in the row order of xyz; every row is written.  fp64 throughout; one
+ *   thread per point, no atomics, no LDS, no workspace; a point's outputs are a function of its fragment alone.
+ *   MVR_EINVAL, scalars first: the rules of mvr_estimate_normals.  M == 0 then returns MVR_OK.  With M > 0: a NULL
+ *   index, xyz, normals, colors, off, intensity or grad, or index_bytes < mvr_radius_index_bytes(M).
+ * ---------------------------------------------------------------------- */
+int mvr_color_gradient(const void* index, size_t index_bytes, const double* xyz, const double* normals,
+                       const double* colors, const int64_t* off, int B, int64_t M, double r_index, double radius,
+                       double* intensity, double* grad, int32_t* n_nbr, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Coloured ICP refinement, batched over pairs (csrc/icp_colored.hip): the loop of Park, Zhou and
+ * Koltun's coloured ICP (2017), Open3D's registration_colored_icp, restated from the maths; Open3D parity is
+ * unpinned.  The arguments are those of mvr_icp_refine_plane plus intensity [M], grad [M,3] (mvr_color_gradient's
+ * outputs, the row order of xyz), lambda_geometric, and mvr_icp_refine_robust's kernel, kernel_k and w_sum.
+ *   eval(T), fitness, rmse, n_corr: exactly mvr_icp_refine's (Euclidean distances), so the methods' figures compare.
+ *   Loop: state = eval(T0); up to max_iters times: stop with status bit 1 when n_corr < 6.  Over the valid pairs, for
+ *   source row i moved to q = T x_i and matched with target row t: y its point, n its normal, d its gradient,
+ *   c = the target fragment's first point (the per-pair origin of mvr_icp_refine_plane), lambda = lambda_geometric:
+ *     e = q - y;  g = e . n;  r_I = I[i] - (I[t] + d . (e - g n));  dM = -(d - (d . n) n)
+ *     J_G = [(q - c) x n, n],  J_I = [(q - c) x dM, dM]
+ *     w_G = w(sqrt(lambda) g),  w_I = w(sqrt(1 - lambda) r_I)     (the kernel sees the scaled residuals, as Open3D's)
+ *     H = sum lambda w_G J_G J_G^T + (1 - lambda) w_I J_I J_I^T
+ *     b = sum lambda w_G J_G g + (1 - lambda) w_I J_I r_I;  solve H xi = -b by Cholesky.
+ *   The pivot rule with status bit 8, the increment about c, T <- D T, the stopping rule, bits 2 and 4, the trace, the
+ *   NULL outputs and the invalid-pair behaviour are mvr_icp_refine_plane's.  lambda == 1 is the point-to-plane solve.
+ *   kernel, kernel_k: mvr_icp_refine_robust's weights w(r); MVR_KERNEL_L2 is the plain loop (no weight is computed).
+ *   w_sum [P] (may be NULL): sum (lambda w_G + (1 - lambda) w_I) over the valid correspondences of the returned T's
+ *   evaluation; with L2 that is n_corr exactly; 0 for an invalid pair.
+ *   fp64 throughout; one workgroup per pair, every iteration inside the one launch, no atomics, no workspace, the
+ *   reduction in a fixed order; a pair's outputs are a function of the pair alone.
+ *   MVR_EINVAL, scalars first: lambda_geometric outside [0, 1] (a NaN included); a kernel outside its range; for a
+ *   kernel other than L2 a kernel_k that is not > 0; the rules of mvr_icp_refine.  P == 0 then returns MVR_OK.  With
+ *   P > 0 and M > 0 also a NULL normals, intensity or grad.
+ * ---------------------------------------------------------------------- */
+int mvr_icp_refine_colored(const void* index, size_t index_bytes, const double* xyz, const double* normals,
+                           const double* intensity, const double* grad, const int64_t* off, int B, int64_t M,
+                           double r_index, const int64_t* pairs, const double* T0, int P, double max_dist,
+                           double lambda_geometric, int kernel, double kernel_k, int max_iters, double tol_fitness,
+                           double tol_rmse, double* T, double* fitness, double* rmse, int32_t* n_corr, int32_t* iters,
+                           int32_t* status, double* trace, double* w_sum, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Per-pair 6 x 6 information matrices on a radius index (csrc/info.hip): what Open3D's

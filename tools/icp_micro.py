@@ -7,14 +7,19 @@ mvr_radius_overlap_count call on the same index (one 27-cell walk with early exi
 the host oracle (tests/icp_oracle.py: sklearn kd-tree + numpy SVD) on the first --host_pairs pairs.  HIP events around
 each call after a warm-up, median over --reps calls.  point_to_plane and generalized also time the normal estimation
 (radius = the cell; generalized takes --epsilon), and every method reports the iterations to convergence at
-tolerances 1e-6 from the same starts.  --kernel NAME[:K] sends the same calls through csrc/icp_robust.hip
+tolerances 1e-6 from the same starts.  --method colored (csrc/icp_colored.hip mvr_icp_refine_colored)
+gives the fragments the colours of tests/colored_icp_oracle.py's field, times csrc/color_grad.hip mvr_color_gradient
+beside the normals and runs the point-to-plane calls first, in the same process, so the two methods' figures stand
+side by side; with --kernel it goes through its own entry's robust kernels.  --kernel NAME[:K] sends the same calls through csrc/icp_robust.hip
 mvr_icp_refine_robust with that robust kernel (l2, huber, cauchy, gm, tukey; K defaults to the voxel size): l2 against
 a run without the flag is what the weighted path costs, tukey against l2 what a kernel costs.
 A library built with another workgroup size (tools/build_variant.sh icp.hip icp512 -DMVR_ICP_THREADS=512, or
 icp_plane.hip plane512 -DMVR_ICP_PLANE_THREADS=512, icp_gicp.hip gicp512 -DMVR_ICP_GICP_THREADS=512, normals.hip
-nrm256 -DMVR_NORMALS_THREADS=256; MVR_LIB=tools/vsp/icp512.so) times that variant.
-usage: python tools/icp_micro.py [--method point_to_point|point_to_plane|generalized] [--epsilon 1e-3] [--frags 30]
-                                 [--reps 7] [--host_pairs 4] [--kernel tukey:0.025]"""
+nrm256 -DMVR_NORMALS_THREADS=256, icp_colored.hip col512 -DMVR_ICP_COLORED_THREADS=512, color_grad.hip cg256
+-DMVR_COLOR_GRAD_THREADS=256; MVR_LIB=tools/vsp/icp512.so) times that variant.
+usage: python tools/icp_micro.py [--method point_to_point|point_to_plane|generalized|colored] [--epsilon 1e-3]
+                                 [--lambda_geometric 0.968] [--frags 30] [--reps 7] [--host_pairs 4]
+                                 [--kernel tukey:0.025]"""
 import argparse
 import os
 import sys
@@ -37,13 +42,21 @@ def main():
     ap.add_argument("--frags", type=int, default=30)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--host_pairs", type=int, default=4)
-    ap.add_argument("--method", default="point_to_point", choices=["point_to_point", "point_to_plane", "generalized"])
+    ap.add_argument("--method", default="point_to_point", choices=["point_to_point", "point_to_plane", "generalized",
+                                                                      "colored"])
     ap.add_argument("--epsilon", type=float, default=1e-3)
+    ap.add_argument("--lambda_geometric", type=float, default=0.968)
     ap.add_argument("--kernel", default=None, metavar="NAME[:K]")
     a = ap.parse_args()
     d = torch.device("cuda")
     frags, poses = synth_scene_fragments(n_frag=a.frags)
-    fo = FragmentOverlap(frags, "FCGF", 0.025)
+    colored = a.method == "colored"
+    if colored:
+        import colored_icp_oracle as CO
+        world = [np.asarray(f, np.float64) @ poses[b][:3, :3].T + poses[b][:3, 3] for b, f in enumerate(frags)]
+        fo = FragmentOverlap(frags, "FCGF", 0.025, colors=[CO.color_field(w) for w in world])
+    else:
+        fo = FragmentOverlap(frags, "FCGF", 0.025)
     sizes = np.diff(fo.off)
     pairs = np.array([(i, j) for i in range(a.frags) for j in range(i + 1, a.frags)], np.int64)
     rng = np.random.default_rng(0)
@@ -81,7 +94,7 @@ def main():
         name, _, k = a.kernel.partition(":")
         kernel, kernel_k = ROBUST_KERNELS.index(name), float(k) if k else 0.025
         print("through mvr_icp_refine_robust: kernel %s, k %g" % (name, kernel_k), flush=True)
-    if plane or gicp:
+    if plane or gicp or colored:
         nrm = torch.empty(fo.M, 3, dtype=torch.float64, device=d)
         nnb = torch.empty(fo.M, dtype=torch.int32, device=d)
 
@@ -91,8 +104,20 @@ def main():
         ms = timed(normals)
         print("mvr_estimate_normals, %d points, radius %.3f: median %.3f ms (min %.3f, max %.3f); neighbours %d..%d"
               % (fo.M, fo.r, ms[len(ms) // 2], ms[0], ms[-1], int(nnb.min()), int(nnb.max())), flush=True)
+    if colored:
+        inten = torch.empty(fo.M, dtype=torch.float64, device=d)
+        grad = torch.empty(fo.M, 3, dtype=torch.float64, device=d)
 
-    def bench(rows, iters, what, tol=0.0):
+        def gradients():
+            assert L.mvr_color_gradient(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm), N.ptr(fo.colors),
+                                        N.ptr(fo.off_dev), fo.B, fo.M, fo.r, fo.r, N.ptr(inten), N.ptr(grad),
+                                        N.ptr(nnb), N.stream()) == 0
+        ms = timed(gradients)
+        print("mvr_color_gradient, %d points, radius %.3f: median %.3f ms (min %.3f, max %.3f); largest gradient %.3g"
+              % (fo.M, fo.r, ms[len(ms) // 2], ms[0], ms[-1], float(grad.abs().max())), flush=True)
+
+    def bench(rows, iters, what, tol=0.0, method=a.method):
+        plane, gicp, colored = method == "point_to_plane", method == "generalized", method == "colored"
         P = len(rows)
         gp, gT = gp_all[rows].contiguous(), gT_all[rows].contiguous()
         T = torch.empty(P, 12, dtype=torch.float64, device=d)
@@ -103,10 +128,16 @@ def main():
                 N.ptr(it), N.ptr(st), None, N.stream())
 
         def run():
-            if a.kernel is not None:
+            if colored:
+                assert L.mvr_icp_refine_colored(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
+                                                N.ptr(inten), N.ptr(grad), N.ptr(fo.off_dev), fo.B, fo.M, *tail[:5],
+                                                a.lambda_geometric, kernel if a.kernel is not None else 0,
+                                                kernel_k if a.kernel is not None else 0.0, *tail[5:-1], None,
+                                                tail[-1]) == 0
+            elif a.kernel is not None:
                 assert L.mvr_icp_refine_robust(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(nrm),
                                                N.ptr(fo.off_dev), fo.B, fo.M, *tail[:4],
-                                               ["point_to_point", "point_to_plane", "generalized"].index(a.method),
+                                               ["point_to_point", "point_to_plane", "generalized"].index(method),
                                                tail[4], a.epsilon, kernel, kernel_k, *tail[5:-1], None,
                                                tail[-1]) == 0
             elif gicp:
@@ -124,15 +155,19 @@ def main():
             its = it.cpu().numpy()
             print("%s %s, tolerances %g, cap %d: median %.3f ms (min %.3f, max %.3f); iterations min %d, median %d, "
                   "mean %.1f, max %d; %d of %d at the cap; rmse mean %.4f"
-                  % (a.method, what, tol, iters, ms[len(ms) // 2], ms[0], ms[-1], its.min(), int(np.median(its)),
+                  % (method, what, tol, iters, ms[len(ms) // 2], ms[0], ms[-1], its.min(), int(np.median(its)),
                      its.mean(), its.max(), int((st.cpu().numpy() & 2 != 0).sum()), P, float(rm.mean())), flush=True)
             return ms[len(ms) // 2]
-        print("icp %s, %d iterations: median %.3f ms (min %.3f, max %.3f, %d calls); fitness %.3f..%.3f, rmse mean "
-              "%.4f, status %s" % (what, iters, ms[len(ms) // 2], ms[0], ms[-1], a.reps, float(fit.min()),
+        print("%s %s, %d iterations: median %.3f ms (min %.3f, max %.3f, %d calls); fitness %.3f..%.3f, rmse mean "
+              "%.4f, status %s" % (method, what, iters, ms[len(ms) // 2], ms[0], ms[-1], a.reps, float(fit.min()),
                                    float(fit.max()), float(rm.mean()), sorted(set(st.tolist()))), flush=True)
         return ms[len(ms) // 2]
 
     every = torch.arange(len(pairs), device=d)
+    if colored:      # point-to-plane first, in the same process: the figures the coloured ones stand beside
+        p1 = bench(every, 1, "%d pairs" % len(pairs), method="point_to_plane")
+        p30 = bench(every, 30, "%d pairs" % len(pairs), method="point_to_plane")
+        print("point_to_plane per evaluation: %.3f ms over the scene" % ((p30 - p1) / 29.0), flush=True)
     t0 = bench(every, 0, "%d pairs" % len(pairs))
     t1 = bench(every, 1, "%d pairs" % len(pairs))
     t30 = bench(every, 30, "%d pairs" % len(pairs))
@@ -156,7 +191,7 @@ def main():
           "alone (0 iterations) %.3f ms" % (len(pairs), ms[len(ms) // 2], ms[0], ms[-1], t0), flush=True)
 
     host = []
-    for k in range(0 if plane or gicp else min(a.host_pairs, len(pairs))):
+    for k in range(0 if plane or gicp or colored else min(a.host_pairs, len(pairs))):
         i, j = pairs[k]
         t = time.perf_counter()
         r = O.icp(cent[i], cent[j], T0[k], fo.r, 30, 0.0, 0.0)
