@@ -55,13 +55,12 @@ __global__ __launch_bounds__(kColorGradThreads) void color_grad_kernel(RIndex ix
                                                                        int32_t* __restrict__ n_nbr) {
   const int64_t s = (int64_t)blockIdx.x * kColorGradThreads + threadIdx.x;
   if (s >= M) return;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  int64_t i;
+  int b, n;
+  double p[3], A[6], h[3];
+  point_at(ix, xyz, s, i, b, p);
   const double nv[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
   const double f0 = intensity_of(colors, i);
-  int n;
-  double A[6], h[3];
   ball_tangent_sums(ix, xyz, b, p, nv, f0, r, radius, [&](int64_t t) { return intensity_of(colors, t); }, n, A, h);
   double d[3] = {0.0, 0.0, 0.0};
   if (n >= 4) {
@@ -83,16 +82,10 @@ extern "C" int mvr_color_gradient(const void* index, size_t index_bytes, const d
                                   const double* colors, const int64_t* off, int B, int64_t M, double r_index,
                                   double radius, double* intensity, double* grad, int32_t* n_nbr,
                                   hipStream_t stream) {
-  if (M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return MVR_EINVAL;
-  if (!(radius > 0.0) || !(r_index > 0.0) || radius > r_index) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, radius)) return MVR_EINVAL;
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !normals || !colors || !off || !intensity || !grad ||
-      index_bytes < mvr_radius_index_bytes(M))
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !normals || !colors || !intensity || !grad)
     return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
-  const unsigned blocks = (unsigned)((M + mvr::kColorGradThreads - 1) / mvr::kColorGradThreads);
-  hipLaunchKernelGGL(mvr::color_grad_kernel, dim3(blocks), dim3(mvr::kColorGradThreads), 0, stream, ix, xyz, normals,
-                     colors, M, r_index, radius, intensity, grad, n_nbr);
-  MVR_CHECK_LAUNCH();
-  return MVR_OK;
+  return mvr::launch_per_point<mvr::kColorGradThreads>(mvr::color_grad_kernel, index, M, 0, stream, xyz, normals, colors,
+                                                       M, r_index, radius, intensity, grad, n_nbr);
 }

@@ -1,6 +1,6 @@
-// The covariance of a ball's points and the 3 x 3 symmetric Jacobi eigen-solver, shared by the normals (normals.hip)
-// and the ISS saliency (iss.hip), and the tangent-plane sums of the colour gradients (color_grad.hip).  fp64,
-// registers only; every loop is bounded (ball_walk's, the Jacobi sweep cap).
+// The sums over rindex.hpp's ball_walk that its per-point kernels share: a ball's covariance and the 3 x 3 symmetric
+// Jacobi eigen-solver (normals.hip: with eigenvectors, iss.hip: without), and the tangent-plane sums of the colour
+// gradients (color_grad.hip).  fp64, registers only; every loop is bounded (ball_walk's, the Jacobi sweep cap).
 #pragma once
 #include "common.hpp"
 #include "rindex.hpp"
@@ -67,7 +67,7 @@ __device__ __forceinline__ void ball_sums(const RIndex& ix, const double* __rest
                                           double (&S)[6]) {
   int k = 0;
   double sm[3] = {0.0, 0.0, 0.0}, sS[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t, double ex, double ey, double ez) {
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t, int, double ex, double ey, double ez) {
     ++k;
     sm[0] += ex; sm[1] += ey; sm[2] += ez;
     sS[0] += ex * ex; sS[1] += ex * ey; sS[2] += ex * ez;
@@ -87,7 +87,7 @@ __device__ __forceinline__ void ball_tangent_sums(const RIndex& ix, const double
                                                   double radius, F&& value, int& n, double (&A)[6], double (&h)[3]) {
   int k = 0;
   double sA[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, sh[3] = {0.0, 0.0, 0.0};
-  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, double ex, double ey, double ez) {
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, int, double ex, double ey, double ez) {
     ++k;
     const double en = ex * nv[0] + ey * nv[1] + ez * nv[2];
     const double ux = ex - en * nv[0], uy = ey - en * nv[1], uz = ez - en * nv[2];

@@ -2,7 +2,7 @@
 // Feature Histogram of Rusu et al. (PCL's FPFHEstimation, Open3D's compute_fpfh_feature) restated from the maths.
 //
 // Two launches, one thread per point in both, fp64 geometry, no atomics.  Thread s takes the point at position s of
-// the index's sorted order, as normals.hip does, and walks the 27 cells with the same box-distance skip.
+// the index's sorted order and walks its ball with rindex.hpp's ball_walk, as normals.hip does.
 //   spfh_kernel: the three angular features of every (point, neighbour) pair, binned into 3 x 11 integer counters;
 //                the counters live in LDS, one column per thread (a register array indexed by a computed bin would go
 //                to scratch), and leave as 100 count / k in fp64 to the workspace row s (the sorted position: the
@@ -28,16 +28,6 @@ __device__ __forceinline__ int bin11(double x) {   // x in bin units; NaN conver
   return b < 0 ? 0 : (b > 10 ? 10 : b);
 }
 
-// lower bound of the squared distance from the point to the cell (dx, dy, dz) of its 27 (normals.hip)
-__device__ __forceinline__ double box_dist2(const double (&lo)[3], double r, double slack, int cell, int& dx, int& dy,
-                                            int& dz) {
-  dx = cell % 3 - 1, dy = (cell / 3) % 3 - 1, dz = cell / 9 - 1;
-  const double gx = dx == 0 ? 0.0 : fmax((dx < 0 ? lo[0] : r - lo[0]) - slack, 0.0);
-  const double gy = dy == 0 ? 0.0 : fmax((dy < 0 ? lo[1] : r - lo[1]) - slack, 0.0);
-  const double gz = dz == 0 ? 0.0 : fmax((dz < 0 ? lo[2] : r - lo[2]) - slack, 0.0);
-  return gx * gx + gy * gy + gz * gz;
-}
-
 __global__ __launch_bounds__(kFpfhThreads) void spfh_kernel(RIndex ix, const double* __restrict__ xyz,
                                                             const double* __restrict__ normals, int64_t M, double r,
                                                             double radius, double* __restrict__ spfh_ws,
@@ -48,51 +38,36 @@ __global__ __launch_bounds__(kFpfhThreads) void spfh_kernel(RIndex ix, const dou
   uint32_t* my = cnt + threadIdx.x;
 #pragma unroll
   for (int c = 0; c < kFpfhBins; ++c) my[c * kFpfhStride] = 0u;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  int64_t i;
+  int b, k = 0;
+  double p[3];
+  point_at(ix, xyz, s, i, b, p);
   const double ni[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
-  const double slack = 1e-9 * r, rad2 = radius * radius * (1.0 + 1e-9);
   const double kPi = 3.14159265358979323846;
-  int64_t c[3];
-  double lo[3];
-  for (int e = 0; e < 3; ++e) {
-    const double cf = floor(p[e] / r);
-    c[e] = (int64_t)cf + OV_BIAS;
-    lo[e] = p[e] - cf * r;
-  }
-  int k = 0;
-  for (int cell = 0; cell < 27; ++cell) {
-    int dx, dy, dz;
-    if (box_dist2(lo, r, slack, cell, dx, dy, dz) > rad2) continue;
-    const int2 se = cell_find(ix, pack_key(b, c[0] + dx, c[1] + dy, c[2] + dz));
-    for (int j = se.x; j < se.y; ++j) {
-      const int64_t t = ix.sidx[j];
-      double ex = xyz[3 * t] - p[0], ey = xyz[3 * t + 1] - p[1], ez = xyz[3 * t + 2] - p[2];
-      const double d = sqrt(ex * ex + ey * ey + ez * ez);
-      if (t == i || !(d < radius)) continue;
-      ++k;
-      if (d == 0.0) continue;
-      const double nj[3] = {normals[3 * t], normals[3 * t + 1], normals[3 * t + 2]};
-      const double a1 = (ni[0] * ex + ni[1] * ey + ni[2] * ez) / d;
-      const double a2 = (nj[0] * ex + nj[1] * ey + nj[2] * ez) / d;
-      const bool swap = fabs(a1) < fabs(a2);
-      const double na0 = swap ? nj[0] : ni[0], na1 = swap ? nj[1] : ni[1], na2 = swap ? nj[2] : ni[2];
-      const double nb0 = swap ? ni[0] : nj[0], nb1 = swap ? ni[1] : nj[1], nb2 = swap ? ni[2] : nj[2];
-      const double f2 = swap ? -a2 : a1;
-      if (swap) { ex = -ex; ey = -ey; ez = -ez; }
-      double v0 = ey * na2 - ez * na1, v1 = ez * na0 - ex * na2, v2 = ex * na1 - ey * na0;   // e x n_a
-      const double vl = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-      if (!(vl > 0.0)) continue;
-      v0 /= vl; v1 /= vl; v2 /= vl;
-      const double w0 = na1 * v2 - na2 * v1, w1 = na2 * v0 - na0 * v2, w2 = na0 * v1 - na1 * v0;   // n_a x v
-      const double f0 = atan2(w0 * nb0 + w1 * nb1 + w2 * nb2, na0 * nb0 + na1 * nb1 + na2 * nb2);
-      const double f1 = v0 * nb0 + v1 * nb1 + v2 * nb2;
-      my[bin11(11.0 * (f0 + kPi) / (2.0 * kPi)) * kFpfhStride] += 1u;
-      my[(11 + bin11(11.0 * (f1 + 1.0) / 2.0)) * kFpfhStride] += 1u;
-      my[(22 + bin11(11.0 * (f2 + 1.0) / 2.0)) * kFpfhStride] += 1u;
-    }
-  }
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, int, double ex, double ey, double ez) {
+    if (t == i) return;
+    ++k;
+    const double d = sqrt(ex * ex + ey * ey + ez * ez);
+    if (d == 0.0) return;
+    const double nj[3] = {normals[3 * t], normals[3 * t + 1], normals[3 * t + 2]};
+    const double a1 = (ni[0] * ex + ni[1] * ey + ni[2] * ez) / d;
+    const double a2 = (nj[0] * ex + nj[1] * ey + nj[2] * ez) / d;
+    const bool swap = fabs(a1) < fabs(a2);
+    const double na0 = swap ? nj[0] : ni[0], na1 = swap ? nj[1] : ni[1], na2 = swap ? nj[2] : ni[2];
+    const double nb0 = swap ? ni[0] : nj[0], nb1 = swap ? ni[1] : nj[1], nb2 = swap ? ni[2] : nj[2];
+    const double f2 = swap ? -a2 : a1;
+    if (swap) { ex = -ex; ey = -ey; ez = -ez; }
+    double v0 = ey * na2 - ez * na1, v1 = ez * na0 - ex * na2, v2 = ex * na1 - ey * na0;   // e x n_a
+    const double vl = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+    if (!(vl > 0.0)) return;
+    v0 /= vl; v1 /= vl; v2 /= vl;
+    const double w0 = na1 * v2 - na2 * v1, w1 = na2 * v0 - na0 * v2, w2 = na0 * v1 - na1 * v0;   // n_a x v
+    const double f0 = atan2(w0 * nb0 + w1 * nb1 + w2 * nb2, na0 * nb0 + na1 * nb1 + na2 * nb2);
+    const double f1 = v0 * nb0 + v1 * nb1 + v2 * nb2;
+    my[bin11(11.0 * (f0 + kPi) / (2.0 * kPi)) * kFpfhStride] += 1u;
+    my[(11 + bin11(11.0 * (f1 + 1.0) / 2.0)) * kFpfhStride] += 1u;
+    my[(22 + bin11(11.0 * (f2 + 1.0) / 2.0)) * kFpfhStride] += 1u;
+  });
   const double dk = (double)k;
 #pragma unroll
   for (int cb = 0; cb < kFpfhBins; ++cb) {
@@ -108,35 +83,20 @@ __global__ __launch_bounds__(kFpfhThreads) void fpfh_kernel(RIndex ix, const dou
                                                             float* __restrict__ fpfh) {
   const int64_t s = (int64_t)blockIdx.x * kFpfhThreads + threadIdx.x;
   if (s >= M) return;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  const double slack = 1e-9 * r, rad2 = radius * radius * (1.0 + 1e-9);
-  int64_t c[3];
-  double lo[3];
-  for (int e = 0; e < 3; ++e) {
-    const double cf = floor(p[e] / r);
-    c[e] = (int64_t)cf + OV_BIAS;
-    lo[e] = p[e] - cf * r;
-  }
-  double acc[kFpfhBins];
+  int64_t i;
+  int b;
+  double p[3], acc[kFpfhBins];
+  point_at(ix, xyz, s, i, b, p);
 #pragma unroll
   for (int cb = 0; cb < kFpfhBins; ++cb) acc[cb] = 0.0;
-  for (int cell = 0; cell < 27; ++cell) {
-    int dx, dy, dz;
-    if (box_dist2(lo, r, slack, cell, dx, dy, dz) > rad2) continue;
-    const int2 se = cell_find(ix, pack_key(b, c[0] + dx, c[1] + dy, c[2] + dz));
-    for (int j = se.x; j < se.y; ++j) {
-      const int64_t t = ix.sidx[j];
-      const double ex = xyz[3 * t] - p[0], ey = xyz[3 * t + 1] - p[1], ez = xyz[3 * t + 2] - p[2];
-      const double d2 = ex * ex + ey * ey + ez * ez;
-      if (t == i || !(sqrt(d2) < radius) || !(d2 > 0.0)) continue;
-      const double wgt = 1.0 / d2;
-      const double* row = spfh_ws + (int64_t)j * kFpfhBins;
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, int j, double ex, double ey, double ez) {
+    const double d2 = ex * ex + ey * ey + ez * ez;
+    if (t == i || !(d2 > 0.0)) return;
+    const double wgt = 1.0 / d2;
+    const double* row = spfh_ws + (int64_t)j * kFpfhBins;   // the neighbour's row, by its sorted position
 #pragma unroll
-      for (int cb = 0; cb < kFpfhBins; ++cb) acc[cb] += row[cb] * wgt;
-    }
-  }
+    for (int cb = 0; cb < kFpfhBins; ++cb) acc[cb] += row[cb] * wgt;
+  });
   const double* own = spfh_ws + s * kFpfhBins;
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
@@ -159,20 +119,15 @@ extern "C" size_t mvr_compute_fpfh_workspace_bytes(int64_t M) {
 extern "C" int mvr_compute_fpfh(const void* index, size_t index_bytes, const double* xyz, const double* normals,
                                 const int64_t* off, int B, int64_t M, double r_index, double radius, float* fpfh,
                                 float* spfh_out, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return MVR_EINVAL;
-  if (!(radius > 0.0) || !(r_index > 0.0) || radius > r_index) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, radius)) return MVR_EINVAL;
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !off || !normals || !fpfh || !workspace || index_bytes < mvr_radius_index_bytes(M) ||
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !normals || !fpfh || !workspace ||
       workspace_bytes < mvr_compute_fpfh_workspace_bytes(M))
     return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
   double* ws = reinterpret_cast<double*>(workspace);
-  const unsigned blocks = (unsigned)((M + mvr::kFpfhThreads - 1) / mvr::kFpfhThreads);
-  hipLaunchKernelGGL(mvr::spfh_kernel, dim3(blocks), dim3(mvr::kFpfhThreads), 0, stream, ix, xyz, normals, M, r_index,
-                     radius, ws, spfh_out);
-  MVR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(mvr::fpfh_kernel, dim3(blocks), dim3(mvr::kFpfhThreads), 0, stream, ix, xyz, M, r_index, radius,
-                     ws, fpfh);
-  MVR_CHECK_LAUNCH();
-  return MVR_OK;
+  const int rc = mvr::launch_per_point<mvr::kFpfhThreads>(mvr::spfh_kernel, index, M, 0, stream, xyz, normals, M, r_index,
+                                                          radius, ws, spfh_out);
+  if (rc != MVR_OK) return rc;
+  return mvr::launch_per_point<mvr::kFpfhThreads>(mvr::fpfh_kernel, index, M, 0, stream, xyz, M, r_index, radius, ws,
+                                                  fpfh);
 }

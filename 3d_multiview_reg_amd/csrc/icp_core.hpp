@@ -127,7 +127,7 @@ __device__ static bool solve6(const double* h, const double* g, double (&xi)[6])
   return true;
 }
 
-// --------------------------------------------------------------------------------------------- the three ICP kernels
+// --------------------------------------------------------------------------------------------------- the ICP kernels
 struct IcpArgs {
   RIndex ix;
   const double* xyz; const double* normals; const int64_t* off; int B; int64_t M; double r;   // normals, epsilon:
@@ -523,17 +523,13 @@ struct ColoredT : SixDofModelT<Wt> {
 };
 
 // ------------------------------------------------------------------------------------------------------- entry points
-// the value checks every entry makes before it looks at P, and the pointer checks it makes once P > 0
+// the value checks every entry makes before it looks at P: rindex.hpp's, the ball being the search's.  The pointer
+// checks it makes once P > 0 are rindex.hpp's index_pointers_ok
 inline bool search_values_ok(int B, int64_t M, int P, double r_index, double max_dist) {
-  return P >= 0 && M >= 0 && M <= 0x7fffffff && B > 0 && B < (1 << 15) && max_dist > 0.0 && r_index > 0.0 &&
-         !(max_dist > r_index);
-}
-inline bool search_pointers_ok(const void* index, size_t index_bytes, const double* xyz, const int64_t* off,
-                               int64_t M) {
-  return M == 0 || (index && xyz && off && index_bytes >= mvr_radius_index_bytes(M));
+  return P >= 0 && ball_values_ok(B, M, r_index, max_dist);
 }
 
-// The checks the three ICP entries share, then the args.  MVR_EINVAL comes before P == 0, and P == 0 returns MVR_OK
+// The checks the ICP entries share, then the args.  MVR_EINVAL comes before P == 0, and P == 0 returns MVR_OK
 // before any pointer is looked at: the caller returns whatever this returns when that is not MVR_OK or P == 0
 inline int icp_args(IcpArgs& a, const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
                     int64_t M, double r_index, const int64_t* pairs, const double* T0, int P, double max_dist,
@@ -543,7 +539,7 @@ inline int icp_args(IcpArgs& a, const void* index, size_t index_bytes, const dou
     return MVR_EINVAL;
   if (P == 0) return MVR_OK;   // no pairs: NULL pointers allowed
   if (!pairs || !T0 || !T || !fitness || !rmse || !status) return MVR_EINVAL;
-  if (!search_pointers_ok(index, index_bytes, xyz, off, M)) return MVR_EINVAL;
+  if (!index_pointers_ok(index, index_bytes, xyz, off, M)) return MVR_EINVAL;
   a = IcpArgs{};
   if (M > 0) a.ix = index_view(const_cast<void*>(index), M);
   a.xyz = xyz; a.off = M > 0 ? off : nullptr; a.B = B; a.M = M; a.r = r_index;

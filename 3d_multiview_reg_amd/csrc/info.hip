@@ -97,7 +97,7 @@ extern "C" int mvr_pair_information(const void* index, size_t index_bytes, const
   if (!mvr::search_values_ok(B, M, P, r_index, max_dist)) return MVR_EINVAL;
   if (P == 0) return MVR_OK;   // no pairs: NULL pointers allowed
   if (!pairs || !T || !info || !rmse || !status) return MVR_EINVAL;
-  if (!mvr::search_pointers_ok(index, index_bytes, xyz, off, M)) return MVR_EINVAL;
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M)) return MVR_EINVAL;
   mvr::InfoArgs a{};
   if (M > 0) a.ix = mvr::index_view(const_cast<void*>(index), M);
   a.xyz = xyz; a.off = M > 0 ? off : nullptr; a.B = B; a.M = M; a.r = r_index;

@@ -36,11 +36,10 @@ __global__ __launch_bounds__(kIssThreads) void iss_saliency_kernel(RIndex ix, co
                                                                    int32_t* __restrict__ n_nbr) {
   const int64_t s = (int64_t)blockIdx.x * kIssThreads + threadIdx.x;
   if (s >= M) return;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  int n;
-  double m[3], S[6];
+  int64_t i;
+  int b, n;
+  double p[3], m[3], S[6];
+  point_at(ix, xyz, s, i, b, p);
   ball_sums(ix, xyz, b, p, r, radius, n, m, S);
   double sal = -1.0;
   if (n >= min_neighbors) {   // min_neighbors >= 1, and the point is in its own ball
@@ -64,14 +63,14 @@ __global__ __launch_bounds__(kNmsThreads) void radius_nms_kernel(RIndex ix, cons
                                                                  uint8_t* __restrict__ keep) {
   const int64_t s = (int64_t)blockIdx.x * kNmsThreads + threadIdx.x;
   if (s >= M) return;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  int64_t i;
+  int b, n = 0;
+  double p[3];
+  point_at(ix, xyz, s, i, b, p);
   const double si = score[i];
-  int n = 0;
   bool beaten = false;
   // every row t is a row of xyz below M (the index holds nothing else), so score[t] is in bounds
-  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, double, double, double) {
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t t, int, double, double, double) {
     ++n;
     const double sj = score[t];
     if (t != i && (sj > si || (sj == si && t < i))) beaten = true;   // a NaN on either side: false
@@ -81,39 +80,26 @@ __global__ __launch_bounds__(kNmsThreads) void radius_nms_kernel(RIndex ix, cons
 
 }  // namespace mvr
 
-static bool iss_common_invalid(int B, int64_t M, double r_index, double radius, int min_neighbors) {
-  if (M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return true;
-  if (!(radius > 0.0) || !(r_index > 0.0) || radius > r_index) return true;
-  return min_neighbors < 1;
-}
-
 extern "C" int mvr_iss_saliency(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
                                 int64_t M, double r_index, double salient_radius, double gamma_21, double gamma_32,
                                 double min_ratio, int min_neighbors, double* saliency, int32_t* n_nbr,
                                 hipStream_t stream) {
-  if (iss_common_invalid(B, M, r_index, salient_radius, min_neighbors)) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, salient_radius) || min_neighbors < 1) return MVR_EINVAL;
   if (!(gamma_21 > 0.0) || gamma_21 > 1.0 || !(gamma_32 > 0.0) || gamma_32 > 1.0) return MVR_EINVAL;
   if (!(min_ratio >= 0.0) || !(min_ratio < 1.0)) return MVR_EINVAL;
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !off || !saliency || index_bytes < mvr_radius_index_bytes(M)) return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
-  const unsigned blocks = (unsigned)((M + mvr::kIssThreads - 1) / mvr::kIssThreads);
-  hipLaunchKernelGGL(mvr::iss_saliency_kernel, dim3(blocks), dim3(mvr::kIssThreads), 0, stream, ix, xyz, M, r_index,
-                     salient_radius, gamma_21, gamma_32, min_ratio, min_neighbors, saliency, n_nbr);
-  MVR_CHECK_LAUNCH();
-  return MVR_OK;
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !saliency) return MVR_EINVAL;
+  return mvr::launch_per_point<mvr::kIssThreads>(mvr::iss_saliency_kernel, index, M, 0, stream, xyz, M, r_index,
+                                                 salient_radius, gamma_21, gamma_32, min_ratio, min_neighbors, saliency,
+                                                 n_nbr);
 }
 
 extern "C" int mvr_radius_nms(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
                               int64_t M, double r_index, double radius, int min_neighbors, const double* score,
                               uint8_t* keep, hipStream_t stream) {
-  if (iss_common_invalid(B, M, r_index, radius, min_neighbors)) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, radius) || min_neighbors < 1) return MVR_EINVAL;
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !off || !score || !keep || index_bytes < mvr_radius_index_bytes(M)) return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
-  const unsigned blocks = (unsigned)((M + mvr::kNmsThreads - 1) / mvr::kNmsThreads);
-  hipLaunchKernelGGL(mvr::radius_nms_kernel, dim3(blocks), dim3(mvr::kNmsThreads), 0, stream, ix, xyz, M, r_index,
-                     radius, min_neighbors, score, keep);
-  MVR_CHECK_LAUNCH();
-  return MVR_OK;
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !score || !keep) return MVR_EINVAL;
+  return mvr::launch_per_point<mvr::kNmsThreads>(mvr::radius_nms_kernel, index, M, 0, stream, xyz, M, r_index, radius,
+                                                 min_neighbors, score, keep);
 }

@@ -101,14 +101,6 @@ __device__ __forceinline__ double axis_gap(int d, double lo, double r, double sl
   return fmax((d < 0 ? lo : r - lo) + (double)((d < 0 ? -d : d) - 1) * r - slack, 0.0);
 }
 
-// the rows [t0, t1) of fragment b, clamped into [0, M]
-__device__ __forceinline__ void frag_rows(const int64_t* __restrict__ off, int b, int64_t M, int64_t& t0, int64_t& t1) {
-  t0 = off[b];
-  t1 = off[b + 1];
-  t0 = t0 < 0 ? 0 : (t0 > M ? M : t0);
-  t1 = t1 < t0 ? t0 : (t1 > M ? M : t1);
-}
-
 __global__ __launch_bounds__(kKnnThreads) void knn_self_kernel(RIndex ix, const double* __restrict__ xyz,
                                                                const int64_t* __restrict__ off, int64_t M, double r,
                                                                int k, int32_t* __restrict__ idx,
@@ -116,22 +108,15 @@ __global__ __launch_bounds__(kKnnThreads) void knn_self_kernel(RIndex ix, const 
                                                                int32_t* __restrict__ left) {
   const int64_t s = (int64_t)blockIdx.x * kKnnThreads + threadIdx.x;
   if (s >= M) return;   // no barrier below
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  int64_t t0, t1;
+  int64_t i, t0, t1, c[3];
+  int b;
+  double p[3], lo[3], face = r;   // face: the distance to the nearest face of the point's own cell
+  point_at(ix, xyz, s, i, b, p);
   frag_rows(off, b, M, t0, t1);
   const int64_t n_b = t1 - t0;
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
   const double slack = 1e-9 * r;
-  int64_t c[3];
-  double lo[3];   // distance to the lower neighbour cell along each axis; r - lo to the upper one
-  double face = r;
-  for (int e = 0; e < 3; ++e) {
-    const double cf = floor(p[e] / r);
-    c[e] = (int64_t)cf + OV_BIAS;
-    lo[e] = p[e] - cf * r;
-    face = fmin(face, fmin(lo[e], r - lo[e]));
-  }
+  cell_of(p, r, c, lo);
+  for (int e = 0; e < 3; ++e) face = fmin(face, fmin(lo[e], r - lo[e]));
   KnnList L;
   L.init(k, (int)(n_b < k ? (n_b > 0 ? n_b : 1) : k));
   bool resolved = false;
@@ -172,12 +157,12 @@ __global__ __launch_bounds__(kKnnThreads) void knn_fallback_kernel(RIndex ix, co
   for (int64_t q = blockIdx.x; q < n; q += gridDim.x) {   // uniform over the wave, as everything but the scan
     const int64_t s = left[q];
     if (s < 0 || s >= M) continue;
-    const int64_t i = ix.sidx[s];
-    const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-    int64_t t0, t1;
+    int64_t i, t0, t1;
+    int b;
+    double p[3];
+    point_at(ix, xyz, s, i, b, p);
     frag_rows(off, b, M, t0, t1);
     const int64_t n_b = t1 - t0;
-    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     const int kk = (int)(n_b < k ? (n_b > 0 ? n_b : 1) : k);
     // every lane keeps the best kk of its rows t0 + lane, t0 + lane + 64, ...: the best kk of all are among them
     KnnList L;
@@ -220,23 +205,21 @@ extern "C" size_t mvr_knn_self_workspace_bytes(int64_t M) { return mvr::knn_ws_b
 extern "C" int mvr_knn_self(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
                             int64_t M, double r_index, int k, int32_t* idx, double* dist2, void* workspace,
                             size_t workspace_bytes, hipStream_t stream) {
-  if (M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return MVR_EINVAL;
-  if (!(r_index > 0.0) || k < 1 || k > mvr::kKnnMaxK) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, r_index) || k < 1 || k > mvr::kKnnMaxK) return MVR_EINVAL;   // no radius
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !off || !idx || !dist2 || !workspace) return MVR_EINVAL;
-  if (index_bytes < mvr_radius_index_bytes(M) || workspace_bytes < mvr::knn_ws_bytes(M)) return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !idx || !dist2 || !workspace ||
+      workspace_bytes < mvr::knn_ws_bytes(M))
+    return MVR_EINVAL;
   int32_t* n_left = reinterpret_cast<int32_t*>(workspace);          // workspace: the counter, then at 256 the list
   int32_t* left = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + 256);
   if (hipMemsetAsync(n_left, 0, 256, stream) != hipSuccess) return MVR_ELAUNCH;
   const size_t lds = (size_t)k * mvr::kKnnThreads * 12;
-  const unsigned blocks = (unsigned)((M + mvr::kKnnThreads - 1) / mvr::kKnnThreads);
-  hipLaunchKernelGGL(mvr::knn_self_kernel, dim3(blocks), dim3(mvr::kKnnThreads), lds, stream, ix, xyz, off, M,
-                     r_index, k, idx, dist2, n_left, left);
-  MVR_CHECK_LAUNCH();
+  const int rc = mvr::launch_per_point<mvr::kKnnThreads>(mvr::knn_self_kernel, index, M, lds, stream, xyz, off, M,
+                                                         r_index, k, idx, dist2, n_left, left);
+  if (rc != MVR_OK) return rc;
   const unsigned fb = M < mvr::kKnnFallbackBlocks ? (unsigned)M : (unsigned)mvr::kKnnFallbackBlocks;
-  hipLaunchKernelGGL(mvr::knn_fallback_kernel, dim3(fb), dim3(mvr::kKnnThreads), lds, stream, ix, xyz, off, M, k, idx,
-                     dist2, n_left, left);
+  hipLaunchKernelGGL(mvr::knn_fallback_kernel, dim3(fb), dim3(mvr::kKnnThreads), lds, stream,
+                     mvr::index_view(const_cast<void*>(index), M), xyz, off, M, k, idx, dist2, n_left, left);
   MVR_CHECK_LAUNCH();
   return MVR_OK;
 }

@@ -30,10 +30,10 @@ __global__ __launch_bounds__(kNormalsThreads) void normals_kernel(RIndex ix, con
                                                                   int32_t* __restrict__ n_nbr) {
   const int64_t s = (int64_t)blockIdx.x * kNormalsThreads + threadIdx.x;
   if (s >= M) return;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  int n;
+  int64_t i;
+  int b, n;
+  double p[3];
+  point_at(ix, xyz, s, i, b, p);
   double m[3], S[6];   // sum e; sum e e^T: xx xy xz yy yz zz
   ball_sums(ix, xyz, b, p, r, radius, n, m, S);
   double nv[3] = {0.0, 0.0, 1.0};
@@ -63,14 +63,9 @@ __global__ __launch_bounds__(kNormalsThreads) void normals_kernel(RIndex ix, con
 extern "C" int mvr_estimate_normals(const void* index, size_t index_bytes, const double* xyz, const int64_t* off,
                                     int B, int64_t M, double r_index, double radius, const double* viewpoints,
                                     double* normals, int32_t* n_nbr, hipStream_t stream) {
-  if (M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return MVR_EINVAL;
-  if (!(radius > 0.0) || !(r_index > 0.0) || radius > r_index) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, radius)) return MVR_EINVAL;
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !off || !normals || index_bytes < mvr_radius_index_bytes(M)) return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
-  const unsigned blocks = (unsigned)((M + mvr::kNormalsThreads - 1) / mvr::kNormalsThreads);
-  hipLaunchKernelGGL(mvr::normals_kernel, dim3(blocks), dim3(mvr::kNormalsThreads), 0, stream, ix, xyz, M, r_index,
-                     radius, viewpoints, normals, n_nbr);
-  MVR_CHECK_LAUNCH();
-  return MVR_OK;
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !normals) return MVR_EINVAL;
+  return mvr::launch_per_point<mvr::kNormalsThreads>(mvr::normals_kernel, index, M, 0, stream, xyz, M, r_index, radius,
+                                                     viewpoints, normals, n_nbr);
 }

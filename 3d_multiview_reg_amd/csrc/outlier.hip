@@ -39,9 +39,8 @@ __global__ __launch_bounds__(kStatThreads) void statistical_kernel(const double*
 #pragma clang fp contract(off)
   __shared__ double red[kStatThreads];
   const int b = blockIdx.x, tid = threadIdx.x;
-  int64_t t0 = off[b], t1 = off[b + 1];
-  t0 = t0 < 0 ? 0 : (t0 > M ? M : t0);
-  t1 = t1 < t0 ? t0 : (t1 > M ? M : t1);
+  int64_t t0, t1;
+  frag_rows(off, b, M, t0, t1);
   const int64_t n_b = t1 - t0;   // uniform over the workgroup, as every branch on it below
   const double found = (double)(n_b < k ? n_b : k);
   double acc = 0.0;
@@ -76,11 +75,11 @@ __global__ __launch_bounds__(kCountThreads) void radius_count_kernel(RIndex ix, 
                                                                      int32_t* __restrict__ count) {
   const int64_t s = (int64_t)blockIdx.x * kCountThreads + threadIdx.x;
   if (s >= M) return;
-  const int64_t i = ix.sidx[s];
-  const int b = (int)(ix.skey[s] >> (3 * OV_BITS));
-  const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-  int n = 0;
-  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t, double, double, double) { ++n; });
+  int64_t i;
+  int b, n = 0;
+  double p[3];
+  point_at(ix, xyz, s, i, b, p);
+  ball_walk(ix, xyz, b, p, r, radius, [&](int64_t, int, double, double, double) { ++n; });
   count[i] = n;
 }
 
@@ -101,14 +100,9 @@ extern "C" int mvr_statistical_outlier(const double* dist2, const int64_t* off, 
 
 extern "C" int mvr_radius_count(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B,
                                 int64_t M, double r_index, double radius, int32_t* count, hipStream_t stream) {
-  if (M < 0 || M > 0x7fffffff || B <= 0 || B >= (1 << 15)) return MVR_EINVAL;
-  if (!(radius > 0.0) || !(r_index > 0.0) || radius > r_index) return MVR_EINVAL;
+  if (!mvr::ball_values_ok(B, M, r_index, radius)) return MVR_EINVAL;
   if (M == 0) return MVR_OK;   // no points: NULL pointers allowed
-  if (!index || !xyz || !off || !count || index_bytes < mvr_radius_index_bytes(M)) return MVR_EINVAL;
-  const mvr::RIndex ix = mvr::index_view(const_cast<void*>(index), M);
-  const unsigned blocks = (unsigned)((M + mvr::kCountThreads - 1) / mvr::kCountThreads);
-  hipLaunchKernelGGL(mvr::radius_count_kernel, dim3(blocks), dim3(mvr::kCountThreads), 0, stream, ix, xyz, M, r_index,
-                     radius, count);
-  MVR_CHECK_LAUNCH();
-  return MVR_OK;
+  if (!mvr::index_pointers_ok(index, index_bytes, xyz, off, M) || !count) return MVR_EINVAL;
+  return mvr::launch_per_point<mvr::kCountThreads>(mvr::radius_count_kernel, index, M, 0, stream, xyz, M, r_index,
+                                                   radius, count);
 }

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from lib import _native as N
+from lib.overlap import _point_tensor
 
 STATUS_FEW_CORRESPONDENCES, STATUS_ITERATION_CAP, STATUS_INVALID_PAIR = 1, 2, 4
 # the 6 x 6 system is not positive definite to working precision; point-to-point: only with a robust kernel, when the
@@ -85,48 +86,48 @@ def _run(name, fo, pairs, T_in, T_name, max_dist, needs_normals, call, normals_f
         nrm = getattr(fo, "normals", None)
         if nrm is None:
             raise ValueError("%s: %sneeds fo.normals (call fo.estimate_normals())" % (name, normals_for))
-        if not torch.is_tensor(nrm) or tuple(nrm.shape) != (fo.M, 3) or nrm.dtype != torch.float64 or \
-                nrm.device != fo.xyz.device or not nrm.is_contiguous():
-            raise ValueError("%s: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
-                             % (name, fo.M))
+        _point_tensor(name, "normals", nrm, (fo.M, 3), fo.xyz)
     N.require_hip()
     return N.hand_back(call(int(Tin.shape[0]), ij.to(fo.device, torch.int64).contiguous(),
                             Tin[:, :3, :].to(fo.device, torch.float64).contiguous()), T_in)
 
 
 def _refine(name, fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace, entry, needs_normals,
-            normals_for="", epsilon=None, robust=None, return_weight_sum=False):
-    """icp_refine and gicp_refine after their own checks: entry names the C function, which takes the normals when
-    needs_normals and epsilon when that is not None.  robust (_check_kernel's pair) not None: mvr_icp_refine_robust as
-    the method `entry` names, with w_sum when return_weight_sum."""
+            normals_for="", epsilon=None, robust=None, return_weight_sum=False, lambda_geometric=None):
+    """icp_refine, gicp_refine and colored_icp_refine after their own checks: entry names the C function, which takes
+    the normals when needs_normals and epsilon when that is not None.  robust (_check_kernel's pair) not None:
+    mvr_icp_refine_robust as the method `entry` names, with w_sum when return_weight_sum.  lambda_geometric not None:
+    mvr_icp_refine_colored, which takes fo.intensity and fo.color_grad after the normals and robust's pair and w_sum as
+    the robust entry does."""
     def call(P, ij, T0):
         dev = fo.device
         T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
         fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
         n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
         trace = torch.empty(P, int(max_iters) + 1, 2, dtype=torch.float64, device=dev) if return_trace else None
-        head = (N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz)) + \
-            ((N.ptr(fo.normals),) if needs_normals else ()) + (N.ptr(fo.off_dev), fo.B, fo.M)
-        eps = () if epsilon is None else (float(epsilon),)
-        if robust is None:
-            N.check(getattr(N.lib(), entry)(*head, fo.r, N.ptr(ij), N.ptr(T0), P, max_dist, *eps, int(max_iters),
-                                            float(tol_fitness), float(tol_rmse), N.ptr(T), N.ptr(fitness),
-                                            N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace),
-                                            N.stream()), entry)
+        w_sum = torch.empty(P, dtype=torch.float64, device=dev) if return_weight_sum else None
+        nrm = (N.ptr(fo.normals),) if needs_normals else ()
+        pairs_in = (N.ptr(ij), N.ptr(T0), P)
+        settings = (int(max_iters), float(tol_fitness), float(tol_rmse))
+        outs = (N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace))
+        if lambda_geometric is not None:
+            fn, args = "mvr_icp_refine_colored", (
+                *fo._points(), *nrm, N.ptr(fo.intensity), N.ptr(fo.color_grad), *fo._fragments(), *pairs_in, max_dist,
+                float(lambda_geometric), *robust, *settings, *outs, N.ptr(w_sum))
+        elif robust is not None:
+            fn, args = "mvr_icp_refine_robust", (
+                *fo._points(), *(nrm or (None,)), *fo._fragments(), *pairs_in, _METHOD_IDS[entry], max_dist,
+                1.0 if epsilon is None else float(epsilon), *robust, *settings, *outs, N.ptr(w_sum))
         else:
-            w_sum = torch.empty(P, dtype=torch.float64, device=dev) if return_weight_sum else None
-            N.check(N.lib().mvr_icp_refine_robust(
-                N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals) if needs_normals else None,
-                N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(ij), N.ptr(T0), P, _METHOD_IDS[entry], max_dist,
-                1.0 if epsilon is None else float(epsilon), robust[0], robust[1], int(max_iters), float(tol_fitness),
-                float(tol_rmse), N.ptr(T), N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status),
-                N.ptr(trace), N.ptr(w_sum), N.stream()), "mvr_icp_refine_robust")
+            eps = () if epsilon is None else (float(epsilon),)
+            fn, args = entry, (*fo._points(), *nrm, *fo._fragments(), *pairs_in, max_dist, *eps, *settings, *outs)
+        N.check(getattr(N.lib(), fn)(*args, N.stream()), fn)
         T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
         T4[:, :3], T4[:, 3, 3] = T, 1.0
         out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
         if return_trace:
             out["trace"] = trace
-        if robust is not None and return_weight_sum:
+        if return_weight_sum:
             out["w_sum"] = w_sum
         return out
     return _run(name, fo, pairs, T_init, "T_init", max_dist, needs_normals, call, normals_for)
@@ -231,9 +232,9 @@ def information_matrix(fo, pairs, T, max_dist=None, order="redwood"):
         info = torch.empty(P, 36, dtype=torch.float64, device=fo.device)
         rmse = torch.empty(P, dtype=torch.float64, device=fo.device)
         n_corr, status = (torch.empty(P, dtype=torch.int32, device=fo.device) for _ in range(2))
-        N.check(N.lib().mvr_pair_information(N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B,
-                                             fo.M, fo.r, N.ptr(ij), N.ptr(T3), P, max_dist, N.ptr(info), N.ptr(n_corr),
-                                             N.ptr(rmse), N.ptr(status), N.stream()), "mvr_pair_information")
+        N.check(N.lib().mvr_pair_information(*fo._points(), *fo._fragments(), N.ptr(ij), N.ptr(T3), P, max_dist,
+                                             N.ptr(info), N.ptr(n_corr), N.ptr(rmse), N.ptr(status), N.stream()),
+                "mvr_pair_information")
         return {"info": permute_information(info.view(P, 6, 6), order), "n_corr": n_corr, "rmse": rmse,
                 "status": status}
     return _run("information_matrix", fo, pairs, T, "T", max_dist, False, call)
@@ -308,10 +309,7 @@ def _check_colored(name, fo):
         if x is None:
             raise ValueError("%s: needs fo.%s (call %s)" % (name, what, hint))
         shape = (fo.M,) if what == "intensity" else (fo.M, 3)
-        if not torch.is_tensor(x) or tuple(x.shape) != shape or x.dtype != torch.float64 or \
-                x.device != fo.xyz.device or not x.is_contiguous():
-            raise ValueError("%s: fo.%s must be a contiguous fp64 %s tensor on the device of fo.xyz"
-                             % (name, what, list(shape)))
+        _point_tensor(name, what, x, shape, fo.xyz, str(list(shape)))
 
 
 def colored_icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitness=1e-6, tol_rmse=1e-6,
@@ -334,33 +332,11 @@ def colored_icp_refine(fo, pairs, T_init, max_dist=None, max_iters=30, tol_fitne
     _check_settings("colored_icp_refine", max_dist, max_iters, tol_fitness, tol_rmse)
     _check_lambda("colored_icp_refine", float(lambda_geometric))
     robust = _check_kernel("colored_icp_refine", kernel, kernel_k, return_weight_sum and kernel is not None)
-    kernel_id, k = (0, 0.0) if robust is None else robust
-
     if max_dist <= fo.r:       # beyond it _run raises
         _check_colored("colored_icp_refine", fo)
-
-    def call(P, ij, T0):
-        dev = fo.device
-        T = torch.empty(P, 3, 4, dtype=torch.float64, device=dev)
-        fitness, rmse = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
-        n_corr, iters, status = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
-        trace = torch.empty(P, int(max_iters) + 1, 2, dtype=torch.float64, device=dev) if return_trace else None
-        w_sum = torch.empty(P, dtype=torch.float64, device=dev) if return_weight_sum else None
-        N.check(N.lib().mvr_icp_refine_colored(
-            N.ptr(fo.index), fo.index.numel(), N.ptr(fo.xyz), N.ptr(fo.normals), N.ptr(fo.intensity),
-            N.ptr(fo.color_grad), N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(ij), N.ptr(T0), P, max_dist,
-            float(lambda_geometric), kernel_id, k, int(max_iters), float(tol_fitness), float(tol_rmse), N.ptr(T),
-            N.ptr(fitness), N.ptr(rmse), N.ptr(n_corr), N.ptr(iters), N.ptr(status), N.ptr(trace), N.ptr(w_sum),
-            N.stream()), "mvr_icp_refine_colored")
-        T4 = torch.zeros(P, 4, 4, dtype=torch.float64, device=dev)
-        T4[:, :3], T4[:, 3, 3] = T, 1.0
-        out = {"T": T4, "fitness": fitness, "rmse": rmse, "n_corr": n_corr, "iters": iters, "status": status}
-        if return_trace:
-            out["trace"] = trace
-        if return_weight_sum:
-            out["w_sum"] = w_sum
-        return out
-    return _run("colored_icp_refine", fo, pairs, T_init, "T_init", max_dist, True, call)
+    return _refine("colored_icp_refine", fo, pairs, T_init, max_dist, max_iters, tol_fitness, tol_rmse, return_trace,
+                   "mvr_icp_refine_colored", True, robust=robust or (0, 0.0), return_weight_sum=return_weight_sum,
+                   lambda_geometric=lambda_geometric)
 
 
 def colored_icp_pair(src_xyz, src_colors, tgt_xyz, tgt_colors, T_init, max_dist=0.05, voxel_size=None,

@@ -47,15 +47,30 @@ def _statistical_arguments(nb_neighbors, std_ratio):
     return int(nb_neighbors), float(std_ratio)
 
 
+def _ball_radius(name, radius, r, show="%g"):
+    """The check of a ball's radius against r, the index's cell size, that every walk of a ball makes -> the radius as
+    a float.  name: 'entry: argument'; show: how the message prints the value"""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.floating, np.integer)) \
+            or not 0.0 < float(radius) <= r:
+        raise ValueError(("%s " + show + " must lie in (0, %g], the index's cell size (build the FragmentOverlap with "
+                          "radius >= it)") % (name, radius, r))
+    return float(radius)
+
+
+def _point_tensor(name, what, x, shape, xyz, show=None):
+    """The check of a per-point input fo.`what` of a native call: a contiguous fp64 tensor of `shape` on the device of
+    fo.xyz (`xyz`).  show: how the message prints the shape (None: without spaces)"""
+    if not torch.is_tensor(x) or tuple(x.shape) != tuple(shape) or x.dtype != torch.float64 or \
+            x.device != xyz.device or not x.is_contiguous():
+        raise ValueError("%s: fo.%s must be a contiguous fp64 %s tensor on the device of fo.xyz"
+                         % (name, what, show or "[%s]" % ",".join(str(n) for n in shape)))
+
+
 def _radius_outlier_arguments(nb_points, radius, r):
     """radius_outliers' checks that need no device, r the index's cell size -> (nb_points, radius)"""
     if isinstance(nb_points, bool) or int(nb_points) != nb_points or int(nb_points) < 0:
         raise ValueError("radius_outliers: nb_points must be a non-negative integer, not %r" % (nb_points,))
-    radius = float(r if radius is None else radius)
-    if not 0.0 < radius <= r:
-        raise ValueError("radius_outliers: radius %g must lie in (0, %g], the index's cell size (build the "
-                         "FragmentOverlap with radius >= it)" % (radius, r))
-    return int(nb_points), radius
+    return int(nb_points), _ball_radius("radius_outliers: radius", float(r if radius is None else radius), r)
 
 
 ISS_DEFAULTS = {"salient_radius": None, "non_max_radius": None, "gamma_21": 0.975, "gamma_32": 0.975,
@@ -67,13 +82,9 @@ def _iss_arguments(salient_radius, non_max_radius, gamma_21, gamma_32, min_neigh
     gamma_21, gamma_32, min_neighbors, min_ratio) with the defaults filled in (salient r, non-max 2/3 r: Open3D's
     6 : 4 ratio)"""
     r = float(r)
-    radii = []
-    for name, v, default in (("salient_radius", salient_radius, r), ("non_max_radius", non_max_radius, 2.0 * r / 3.0)):
-        v = default if v is None else v
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 < float(v) <= r:
-            raise ValueError("iss_keypoints: %s %r must lie in (0, %g], the index's cell size (build the "
-                             "FragmentOverlap with radius >= it)" % (name, v, r))
-        radii.append(float(v))
+    radii = [_ball_radius("iss_keypoints: " + name, default if v is None else v, r, "%r")
+             for name, v, default in (("salient_radius", salient_radius, r), ("non_max_radius", non_max_radius,
+                                                                              2.0 * r / 3.0))]
     gammas = []
     for name, v in (("gamma_21", gamma_21), ("gamma_32", gamma_32)):
         if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 < float(v) <= 1.0:
@@ -170,17 +181,36 @@ class FragmentOverlap(object):
             self.off = off_raw
             if colors is not None:
                 self.colors = torch.cat([c.to(dev) for c in colors]).reshape(-1, 3).contiguous()
-        self.B, self.M = B, int(self.off[-1])
-        self.off_dev = torch.from_numpy(self.off).to(dev)
-        self.max_points = int(np.max(np.diff(self.off))) if B else 0
-        ib = L.mvr_radius_index_bytes(self.M)
-        self.index = torch.empty(ib, dtype=torch.uint8, device=dev)
-        N.check(L.mvr_radius_index_build(N.ptr(self.xyz), N.ptr(self.off_dev), B, self.M, self.r, N.ptr(self.index),
-                                         ib, N.stream()), "mvr_radius_index_build")
         self.device = dev
+        self._build_index()
+
+    def _build_index(self):
+        """What follows from xyz, off, r and device: B, M, off_dev, max_points and the radius index; what depends on
+        neighbourhoods starts out None"""
+        self.B, self.M = len(self.off) - 1, int(self.off[-1])
+        self.off_dev = torch.from_numpy(self.off).to(self.device)
+        self.max_points = int(np.max(np.diff(self.off))) if self.B else 0
+        ib = N.lib().mvr_radius_index_bytes(self.M)
+        self.index = torch.empty(ib, dtype=torch.uint8, device=self.device)
+        N.check(N.lib().mvr_radius_index_build(N.ptr(self.xyz), *self._fragments(), N.ptr(self.index), ib, N.stream()),
+                "mvr_radius_index_build")
         self.normals = self.n_nbr = None   # set by estimate_normals, or normals assigned by the caller
         self.fpfh = None                   # set by compute_fpfh
         self.intensity = self.color_grad = self.color_n_nbr = None   # set by compute_color_gradients
+
+    def _points(self):
+        """the leading arguments of a native call on the index: index, index_bytes, xyz"""
+        return N.ptr(self.index), self.index.numel(), N.ptr(self.xyz)
+
+    def _fragments(self):
+        """the arguments that follow them (after the per-point inputs of the call, if any): off, B, M, r_index"""
+        return N.ptr(self.off_dev), self.B, self.M, self.r
+
+    def _kept(self, keep):
+        """keep bool [M] on the device -> (rows int64 [K], the kept rows ascending, on the device; numpy int64 [B+1],
+        the prefix sums of the kept points per fragment)"""
+        kept_before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), keep.long().cumsum(0)])
+        return torch.nonzero(keep).reshape(-1), kept_before.cpu().numpy()[self.off].astype(np.int64)
 
     def estimate_normals(self, radius=None, viewpoints=None):
         """Per-point normals of every fragment (csrc/normals.hip mvr_estimate_normals: Open3D's estimate_normals with
@@ -189,10 +219,7 @@ class FragmentOverlap(object):
         viewpoints [B,3] (one per fragment): normals point towards them; None: the sign is unspecified.
         Stores and returns fo.normals (fp64 [M,3], device, the row order of fo.xyz); fo.n_nbr (int32 [M]) holds the
         neighbour counts."""
-        radius = float(self.r if radius is None else radius)
-        if not 0.0 < radius <= self.r:
-            raise ValueError("estimate_normals: radius %g must lie in (0, %g], the index's cell size (build the "
-                             "FragmentOverlap with radius >= it)" % (radius, self.r))
+        radius = _ball_radius("estimate_normals: radius", float(self.r if radius is None else radius), self.r)
         vp = None
         if viewpoints is not None:
             vp = torch.as_tensor(np.asarray(viewpoints) if not torch.is_tensor(viewpoints) else viewpoints)
@@ -201,9 +228,8 @@ class FragmentOverlap(object):
             vp = vp.to(self.device, torch.float64).contiguous()
         normals = torch.empty(self.M, 3, dtype=torch.float64, device=self.device)
         n_nbr = torch.empty(self.M, dtype=torch.int32, device=self.device)
-        N.check(N.lib().mvr_estimate_normals(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz),
-                                             N.ptr(self.off_dev), self.B, self.M, self.r, radius, N.ptr(vp),
-                                             N.ptr(normals), N.ptr(n_nbr), N.stream()), "mvr_estimate_normals")
+        N.check(N.lib().mvr_estimate_normals(*self._points(), *self._fragments(), radius, N.ptr(vp), N.ptr(normals),
+                                             N.ptr(n_nbr), N.stream()), "mvr_estimate_normals")
         self.normals, self.n_nbr = normals, n_nbr
         return normals
 
@@ -213,24 +239,17 @@ class FragmentOverlap(object):
         `radius` (None: fo.r; at most fo.r).  Needs fo.normals (from estimate_normals or assigned by the caller);
         their sign matters, so orient them, e.g. with estimate_normals(viewpoints=...).
         Stores and returns fo.fpfh (fp32 [M,33], device, the row order of fo.xyz)."""
-        radius = float(self.r if radius is None else radius)
-        if not 0.0 < radius <= self.r:
-            raise ValueError("compute_fpfh: radius %g must lie in (0, %g], the index's cell size (build the "
-                             "FragmentOverlap with radius >= it)" % (radius, self.r))
+        radius = _ball_radius("compute_fpfh: radius", float(self.r if radius is None else radius), self.r)
         nrm = self.normals
         if nrm is None:
             raise ValueError("compute_fpfh: needs fo.normals (call fo.estimate_normals(viewpoints=...))")
-        if not torch.is_tensor(nrm) or tuple(nrm.shape) != (self.M, 3) or nrm.dtype != torch.float64 or \
-                nrm.device != self.xyz.device or not nrm.is_contiguous():
-            raise ValueError("compute_fpfh: fo.normals must be a contiguous fp64 [%d,3] tensor on the device of fo.xyz"
-                             % self.M)
+        _point_tensor("compute_fpfh", "normals", nrm, (self.M, 3), self.xyz)
         L = N.lib()
         fpfh = torch.empty(self.M, 33, dtype=torch.float32, device=self.device)
         ws_b = L.mvr_compute_fpfh_workspace_bytes(self.M)
         ws = N.workspace(ws_b, self.device)
-        N.check(L.mvr_compute_fpfh(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(nrm),
-                                   N.ptr(self.off_dev), self.B, self.M, self.r, radius, N.ptr(fpfh), None, N.ptr(ws),
-                                   ws_b, N.stream()), "mvr_compute_fpfh")
+        N.check(L.mvr_compute_fpfh(*self._points(), N.ptr(nrm), *self._fragments(), radius, N.ptr(fpfh), None,
+                                   N.ptr(ws), ws_b, N.stream()), "mvr_compute_fpfh")
         self.fpfh = fpfh
         return fpfh
 
@@ -242,25 +261,18 @@ class FragmentOverlap(object):
         matter).  Stores fo.intensity (fp64 [M]), fo.color_grad (fp64 [M,3]) and fo.color_n_nbr (int32 [M], the
         neighbour counts), device, the row order of fo.xyz, and returns them as a dict of intensity, grad and
         n_nbr."""
-        radius = float(self.r if radius is None else radius)
-        if not 0.0 < radius <= self.r:
-            raise ValueError("compute_color_gradients: radius %g must lie in (0, %g], the index's cell size (build "
-                             "the FragmentOverlap with radius >= it)" % (radius, self.r))
+        radius = _ball_radius("compute_color_gradients: radius", float(self.r if radius is None else radius), self.r)
         if self.colors is None:
             raise ValueError("compute_color_gradients: needs fo.colors (build the FragmentOverlap with colors=...)")
         nrm = self.normals
         if nrm is None:
             raise ValueError("compute_color_gradients: needs fo.normals (call fo.estimate_normals())")
         for what, x in (("normals", nrm), ("colors", self.colors)):
-            if not torch.is_tensor(x) or tuple(x.shape) != (self.M, 3) or x.dtype != torch.float64 or \
-                    x.device != self.xyz.device or not x.is_contiguous():
-                raise ValueError("compute_color_gradients: fo.%s must be a contiguous fp64 [%d,3] tensor on the "
-                                 "device of fo.xyz" % (what, self.M))
+            _point_tensor("compute_color_gradients", what, x, (self.M, 3), self.xyz)
         intensity = torch.empty(self.M, dtype=torch.float64, device=self.device)
         grad = torch.empty(self.M, 3, dtype=torch.float64, device=self.device)
         n_nbr = torch.empty(self.M, dtype=torch.int32, device=self.device)
-        N.check(N.lib().mvr_color_gradient(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(nrm),
-                                           N.ptr(self.colors), N.ptr(self.off_dev), self.B, self.M, self.r, radius,
+        N.check(N.lib().mvr_color_gradient(*self._points(), N.ptr(nrm), N.ptr(self.colors), *self._fragments(), radius,
                                            N.ptr(intensity), N.ptr(grad), N.ptr(n_nbr), N.stream()),
                 "mvr_color_gradient")
         self.intensity, self.color_grad, self.color_n_nbr = intensity, grad, n_nbr
@@ -277,9 +289,8 @@ class FragmentOverlap(object):
         dist2 = torch.empty(self.M, k, dtype=torch.float64, device=self.device)
         ws_b = L.mvr_knn_self_workspace_bytes(self.M)
         ws = N.workspace(ws_b, self.device)
-        N.check(L.mvr_knn_self(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev), self.B,
-                               self.M, self.r, k, N.ptr(idx), N.ptr(dist2), N.ptr(ws), ws_b, N.stream()),
-                "mvr_knn_self")
+        N.check(L.mvr_knn_self(*self._points(), *self._fragments(), k, N.ptr(idx), N.ptr(dist2), N.ptr(ws), ws_b,
+                               N.stream()), "mvr_knn_self")
         return idx, dist2
 
     def statistical_outliers(self, nb_neighbors=20, std_ratio=2.0):
@@ -304,8 +315,7 @@ class FragmentOverlap(object):
         closer than `radius` (None: fo.r; at most fo.r).  -> {"keep": bool [M], "count": int32 [M]} on the device."""
         nb_points, radius = _radius_outlier_arguments(nb_points, radius, self.r)
         count = torch.empty(self.M, dtype=torch.int32, device=self.device)
-        N.check(N.lib().mvr_radius_count(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev),
-                                         self.B, self.M, self.r, radius, N.ptr(count), N.stream()),
+        N.check(N.lib().mvr_radius_count(*self._points(), *self._fragments(), radius, N.ptr(count), N.stream()),
                 "mvr_radius_count")
         return {"keep": count > nb_points, "count": count}
 
@@ -327,16 +337,12 @@ class FragmentOverlap(object):
         saliency = torch.empty(self.M, dtype=torch.float64, device=self.device)
         n_nbr = torch.empty(self.M, dtype=torch.int32, device=self.device)
         keep = torch.empty(self.M, dtype=torch.uint8, device=self.device)
-        N.check(L.mvr_iss_saliency(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev), self.B,
-                                   self.M, self.r, sal_r, g21, g32, min_ratio, min_n, N.ptr(saliency), N.ptr(n_nbr),
-                                   N.stream()), "mvr_iss_saliency")
-        N.check(L.mvr_radius_nms(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz), N.ptr(self.off_dev), self.B,
-                                 self.M, self.r, nms_r, min_n, N.ptr(saliency), N.ptr(keep), N.stream()),
-                "mvr_radius_nms")
+        N.check(L.mvr_iss_saliency(*self._points(), *self._fragments(), sal_r, g21, g32, min_ratio, min_n,
+                                   N.ptr(saliency), N.ptr(n_nbr), N.stream()), "mvr_iss_saliency")
+        N.check(L.mvr_radius_nms(*self._points(), *self._fragments(), nms_r, min_n, N.ptr(saliency), N.ptr(keep),
+                                 N.stream()), "mvr_radius_nms")
         keep = keep.bool()
-        rows = torch.nonzero(keep).reshape(-1)
-        kept_before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), keep.long().cumsum(0)])
-        off = kept_before.cpu().numpy()[self.off].astype(np.int64)
+        rows, off = self._kept(keep)
         return {"keep": keep, "saliency": saliency, "n_nbr": n_nbr, "rows": rows, "off": off}
 
     def select(self, keep):
@@ -346,24 +352,12 @@ class FragmentOverlap(object):
         depend on neighbourhoods).  parent_rows (int64 [M'], device) maps its rows to this object's.
         A fragment may become empty."""
         keep = _keep_mask(keep, self.M).to(self.device)
-        rows = torch.nonzero(keep).reshape(-1)
-        kept_before = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), keep.long().cumsum(0)])
-        off = kept_before.cpu().numpy()[self.off].astype(np.int64)
+        rows, off = self._kept(keep)
         fo = object.__new__(FragmentOverlap)
         fo.method, fo.voxel_size, fo.r, fo.device = self.method, self.voxel_size, self.r, self.device
-        fo.xyz = self.xyz[rows].contiguous()
-        fo.off = off
-        fo.B, fo.M = self.B, int(off[-1])
-        fo.off_dev = torch.from_numpy(off).to(self.device)
-        fo.max_points = int(np.max(np.diff(off))) if fo.B else 0
-        L = N.lib()
-        ib = L.mvr_radius_index_bytes(fo.M)
-        fo.index = torch.empty(ib, dtype=torch.uint8, device=self.device)
-        N.check(L.mvr_radius_index_build(N.ptr(fo.xyz), N.ptr(fo.off_dev), fo.B, fo.M, fo.r, N.ptr(fo.index), ib,
-                                         N.stream()), "mvr_radius_index_build")
-        fo.normals = fo.n_nbr = fo.fpfh = None
+        fo.xyz, fo.off = self.xyz[rows].contiguous(), off
+        fo._build_index()
         fo.colors = None if self.colors is None else self.colors[rows].contiguous()
-        fo.intensity = fo.color_grad = fo.color_n_nbr = None
         fo.parent_rows = rows
         return fo
 
@@ -380,8 +374,7 @@ class FragmentOverlap(object):
         gp = torch.from_numpy(pairs).to(self.device)
         gT = torch.from_numpy(T).to(self.device)
         cnt = torch.empty(max(P, 1), 2, dtype=torch.int32, device=self.device)
-        N.check(N.lib().mvr_radius_overlap_count(N.ptr(self.index), self.index.numel(), N.ptr(self.xyz),
-                                                 N.ptr(self.off_dev), self.B, self.M, N.ptr(gp), N.ptr(gT), P,
+        N.check(N.lib().mvr_radius_overlap_count(*self._points(), *self._fragments()[:3], N.ptr(gp), N.ptr(gT), P,
                                                  self.max_points, self.r, N.ptr(cnt), N.stream()),
                 "mvr_radius_overlap_count")
         return cnt[:P].cpu().numpy()

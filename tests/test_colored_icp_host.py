@@ -294,6 +294,68 @@ def test_colors_argument_of_fragment_overlap_and_register_scene():
         MV.register_scene([None, None], 0.025, method="colored", colors=[None, None], icp_lambda_geometric=1.5)
 
 
+def test_point_tensor_check_through_its_four_callers():
+    """lib.overlap._point_tensor behind compute_fpfh, compute_color_gradients, lib.icp._run and _check_colored: a wrong
+    shape, a wrong dtype and a non-contiguous tensor raise with each caller's own wording, a missing one with its
+    hint"""
+    import re
+    import torch
+    from lib.icp import colored_icp_refine, icp_refine
+    from lib.overlap import FragmentOverlap
+    M, T, pairs = 10, np.tile(np.eye(4), (1, 1, 1)), [[0, 0]]
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float64)
+    bads = (z(M - 1, 3), torch.zeros(M, 3), z(3, M).t())
+
+    def fo(**kw):
+        base = dict(r=0.075, M=M, B=1, xyz=z(M, 3), normals=z(M, 3), colors=z(M, 3), intensity=z(M),
+                    color_grad=z(M, 3), fpfh=None)
+        return types.SimpleNamespace(**dict(base, **kw))
+    tail = " tensor on the device of fo.xyz"
+    callers = (
+        (lambda f: FragmentOverlap.compute_fpfh(f), "normals",
+         "compute_fpfh: fo.normals must be a contiguous fp64 [10,3]" + tail,
+         "compute_fpfh: needs fo.normals (call fo.estimate_normals(viewpoints=...))"),
+        (lambda f: FragmentOverlap.compute_color_gradients(f), "normals",
+         "compute_color_gradients: fo.normals must be a contiguous fp64 [10,3]" + tail,
+         "compute_color_gradients: needs fo.normals (call fo.estimate_normals())"),
+        (lambda f: FragmentOverlap.compute_color_gradients(f), "colors",
+         "compute_color_gradients: fo.colors must be a contiguous fp64 [10,3]" + tail,
+         "compute_color_gradients: needs fo.colors (build the FragmentOverlap with colors=...)"),
+        (lambda f: icp_refine(f, pairs, T, method="point_to_plane"), "normals",
+         "icp_refine: fo.normals must be a contiguous fp64 [10,3]" + tail,
+         "icp_refine: method 'point_to_plane' needs fo.normals (call fo.estimate_normals())"),
+        (lambda f: colored_icp_refine(f, pairs, T), "color_grad",
+         "colored_icp_refine: fo.color_grad must be a contiguous fp64 [10, 3]" + tail,
+         "colored_icp_refine: needs fo.color_grad (call fo.compute_color_gradients())"),
+    )
+    for call, what, wrong, missing in callers:
+        for bad in bads:
+            with pytest.raises(ValueError, match="^" + re.escape(wrong) + "$"):
+                call(fo(**{what: bad}))
+        with pytest.raises(ValueError, match="^" + re.escape(missing) + "$"):
+            call(fo(**{what: None}))
+    for bad in (z(M, 1), torch.zeros(M), z(2 * M)[::2]):
+        with pytest.raises(ValueError, match="^" + re.escape("colored_icp_refine: fo.intensity must be a contiguous "
+                                                             "fp64 [10]" + tail) + "$"):
+            colored_icp_refine(fo(intensity=bad), pairs, T)
+
+
+def test_ball_radius_is_one_rule():
+    import re
+    from lib.overlap import _ball_radius, _iss_arguments, _radius_outlier_arguments
+    r = 0.075
+    assert _ball_radius("f: radius", r, r) == r and _ball_radius("f: radius", 0.05, r) == 0.05
+    for bad in (0.0, -0.01, float("nan"), r * (1.0 + 1e-6)):
+        msg = "f: radius %g must lie in (0, 0.075], the index's cell size (build the FragmentOverlap with radius >= it)"
+        with pytest.raises(ValueError, match="^" + re.escape(msg % bad) + "$"):
+            _ball_radius("f: radius", bad, r)
+        with pytest.raises(ValueError, match="^" + re.escape("radius_outliers: radius %g must lie in" % bad)):
+            _radius_outlier_arguments(16, bad, r)
+        with pytest.raises(ValueError, match="^" + re.escape("iss_keypoints: non_max_radius %r must lie in" % bad)):
+            _iss_arguments(None, bad, 0.975, 0.975, 5, 1e-6, r)
+    assert _radius_outlier_arguments(16, None, r) == (16, r) and _iss_arguments(r, None, 0.975, 0.975, 5, 0.0, r)[0] == r
+
+
 # ----------------------------------------------------------------------------------------- the entry points' checks
 def _colored(L, P=1, M=10, B=2, r=0.075, max_dist=0.05, lam=0.968, kernel=0, k=0.0, iters=30, tf=1e-6, tr=1e-6, ptrs=8,
              index=8, T=8, normals=8, intensity=8, grad=8, index_bytes=None):

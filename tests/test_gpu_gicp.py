@@ -229,6 +229,30 @@ def test_four_entries_share_one_search(gpu):
             assert other["fitness"].tobytes() == ref["fitness"].tobytes()
 
 
+@pytest.mark.parametrize("radius", [0.06, PO.SMALL_R_INDEX])
+def test_per_point_entries_share_one_walk(gpu, radius):
+    """The entries that walk a point's ball on the index (csrc/rindex.hpp ball_walk), on small_normals_case's
+    fragments of 0, 1, 2, 3, 63, 64, 65 and 1025 points at a radius inside the cell and at exactly the cell: the
+    neighbour counts of mvr_estimate_normals, mvr_iss_saliency, mvr_color_gradient and mvr_radius_count are the
+    oracle's, element for element; a point alone in its ball has an all-zero SPFH row; and the seven entries write
+    every row of every output, the neighbours of the empty fragment included."""
+    import point_entries
+    from lib import _native as N
+    frags = PO.small_normals_case()
+    out = {k: v.cpu().numpy() for k, v in point_entries.run(gpu, N.lib(), frags, PO.SMALL_R_INDEX, radius,
+                                                            ks=(20,)).items()}
+    want = np.concatenate([f["n_nbr"] for f in PO.estimate_normals_batch(frags, radius)])
+    print("radius %g: counts %d..%d, %d points alone" % (radius, want.min(), want.max(), (want == 1).sum()))
+    assert want.min() == 1 and want.max() > 50     # no distance is within 1e-7 of either radius: counts are exact
+    for name in ("normals n_nbr", "normals vp n_nbr", "iss n_nbr", "color n_nbr", "count count"):
+        np.testing.assert_array_equal(out[name], want, err_msg=name)
+    assert not out["fpfh spfh"][want == 1].any()
+    for name, x in out.items():
+        if not name.startswith("stat "):
+            sent = point_entries.SENT & 0xff if x.dtype == np.uint8 else point_entries.SENT
+            assert not (x == sent).any(), name
+
+
 # -------------------------------------------------------------------------------------------------------- invariances
 def test_outputs_do_not_depend_on_the_batch(gpu):
     from lib.icp import gicp_refine

@@ -14,7 +14,15 @@ the two files key by key with tobytes().  The case sets:
       42 | 43 | 64 fragments), plus one ragged batch at 2 passes;
     * mvr_posegraph_optimize on every entry of tests/posegraph_oracle.py's cases() with the trace;
     * mvr_posegraph_optimize_lp on the same, with `uncertain` NULL and with every edge flagged uncertain.
-usage: python tools/lib_ab.py LIB_A LIB_B [--cases ransac,graph] [--keep DIR]     exit status 0: every key identical"""
+  points  csrc/rindex.hpp's per-point kernels, every call of tests/helpers/point_entries.py
+    (mvr_estimate_normals without and with viewpoints, mvr_iss_saliency, mvr_radius_nms, mvr_radius_count,
+    mvr_color_gradient, mvr_compute_fpfh with spfh_out, mvr_knn_self at k = 1, 20 and 64, mvr_statistical_outlier) on
+    * tests/icp_plane_oracle.py's small_normals_case (fragments of 0 to 1025 points, cell 0.1) at radius 0.06 and at
+      0.1, exactly the cell;
+    * tests/knn_oracle.py's sparse_case (every query takes the direct scan) and ties_case (a lattice on cell faces
+      with triplicated points), each at its own cell as the radius.
+usage: python tools/lib_ab.py LIB_A LIB_B [--cases ransac,graph,points] [--keep DIR]
+exit status 0: every key identical"""
 import argparse
 import os
 import subprocess
@@ -23,7 +31,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "3d_multiview_reg_amd"), os.path.join(ROOT, "tests"),
-          os.path.join(ROOT, "tests", "golden")):
+          os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "tests", "helpers")):
     sys.path.insert(0, p)
 import numpy as np  # noqa: E402
 
@@ -172,7 +180,19 @@ def graph_cases(d, L, keep):
             keep("posegraph %s %s" % (mode, name), o)
 
 
-CASE_SETS = {"ransac": ransac_cases, "graph": graph_cases}
+def points_cases(d, L, keep):
+    import icp_plane_oracle as PO
+    import knn_oracle as K
+    import point_entries
+    small = PO.small_normals_case()
+    sparse, ties = K.sparse_case(), K.ties_case()
+    for tag, frags, r_index, radius in (("small 0.06", small, PO.SMALL_R_INDEX, 0.06),
+                                        ("small 0.1", small, PO.SMALL_R_INDEX, PO.SMALL_R_INDEX),
+                                        ("sparse", sparse[0], sparse[1], sparse[1]), ("ties", ties[0], ties[1], ties[1])):
+        keep("points " + tag, point_entries.run(d, L, frags, r_index, radius))
+
+
+CASE_SETS = {"ransac": ransac_cases, "graph": graph_cases, "points": points_cases}
 
 
 def main():
