@@ -143,6 +143,9 @@ _SIGS = {
     "mvr_statistical_outlier": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
     "mvr_radius_count": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_vp,
                                  c_vp]),
+    "mvr_dbscan_workspace_bytes": (c_size, [c_i64]),
+    "mvr_cluster_dbscan": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_int,
+                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "mvr_iss_saliency": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_vp, c_vp, c_vp]),
     "mvr_radius_nms": (c_int, [c_vp, c_size, c_vp, c_vp, c_int, c_i64, ctypes.c_double, ctypes.c_double, c_int, c_vp,

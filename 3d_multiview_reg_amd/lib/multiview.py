@@ -432,7 +432,8 @@ def _scene_arguments(n, voxel_size, method, dataset, init, viewpoints, colors=No
 
 
 COARSE_METHODS = ("ransac", "fgr")   # register_scene's step 4: lib.fpfh.register_fpfh / register_fgr
-DENOISE_METHODS = {"statistical": {"nb_neighbors": 20, "std_ratio": 2.0}, "radius": {"nb_points": 16, "radius": None}}
+DENOISE_METHODS = {"statistical": {"nb_neighbors": 20, "std_ratio": 2.0}, "radius": {"nb_points": 16, "radius": None},
+                   "cluster": {"min_points": 10, "min_size": 100, "eps": None}}
 
 
 def _denoise_arguments(denoise, r=None):
@@ -453,6 +454,12 @@ def _denoise_arguments(denoise, r=None):
     d = dict(DENOISE_METHODS[method], **denoise)
     if method == "statistical":
         d["nb_neighbors"], d["std_ratio"] = _statistical_arguments(d["nb_neighbors"], d["std_ratio"])
+    elif method == "cluster":
+        from lib.overlap import _cluster_keep_arguments, _dbscan_arguments
+        rr = float("inf") if r is None else float(r)
+        eps, d["min_points"] = _dbscan_arguments(d["eps"], d["min_points"], rr)
+        d["eps"] = None if d["eps"] is None else eps
+        d["min_size"] = _cluster_keep_arguments(d["min_size"], False)[0]
     else:
         rr = float("inf") if r is None else float(r)
         d["nb_points"], radius = _radius_outlier_arguments(d["nb_points"], rr if d["radius"] is None else d["radius"],
@@ -504,7 +511,10 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
       1b. denoise (None: nothing, the chain and the result as without it): {"method": "statistical", "nb_neighbors":
          20, "std_ratio": 2.0} or {"method": "radius", "nb_points": 16, "radius": None} (options may be left out) —
          fo.statistical_outliers / fo.radius_outliers per fragment, then fo = fo.select(keep): every later stage,
-         the fused scene included, sees the kept points only;
+         the fused scene included, sees the kept points only; or {"method": "cluster", "min_points": 10, "min_size":
+         100, "eps": None} — fo.cluster_dbscan(eps, min_points) per fragment (eps None: the index's cell, at most
+         it), fo.cluster_keep(min_size): the clusters of fewer than min_size points and the noise go, which removes
+         the detached blobs the two outlier filters let through;
       2. estimate_normals(normal_radius, viewpoints) — viewpoints [n,3] in the fragments' own frames, None: their
          origins (where a range sensor stood);
       3. compute_fpfh(fpfh_radius);  4. lib.fpfh.register_fpfh on all pairs i < j with `seed` and
@@ -561,6 +571,8 @@ def register_scene(xyz_list, voxel_size=0.025, method="point_to_point", init=Non
     if denoise is not None:
         if denoise["method"] == "statistical":
             keep = fo.statistical_outliers(denoise["nb_neighbors"], denoise["std_ratio"])["keep"]
+        elif denoise["method"] == "cluster":
+            keep = fo.cluster_keep(fo.cluster_dbscan(denoise["eps"], denoise["min_points"]), denoise["min_size"])
         else:
             keep = fo.radius_outliers(denoise["nb_points"], denoise["radius"])["keep"]
         sizes = np.diff(fo.off)

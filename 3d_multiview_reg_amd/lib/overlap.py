@@ -73,6 +73,28 @@ def _radius_outlier_arguments(nb_points, radius, r):
     return int(nb_points), _ball_radius("radius_outliers: radius", float(r if radius is None else radius), r)
 
 
+def _dbscan_arguments(eps, min_points, r):
+    """cluster_dbscan's checks that need no device, r the index's cell size -> (eps, min_points); eps None: r"""
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) \
+            <= 0x7fffffff:
+        raise ValueError("cluster_dbscan: min_points must be a positive integer, not %r" % (min_points,))
+    if eps is not None and isinstance(eps, (float, np.floating)) and not np.isfinite(eps):
+        raise ValueError("cluster_dbscan: eps must be finite, not %r" % (eps,))
+    return _ball_radius("cluster_dbscan: eps", r if eps is None else eps, r, "%r"), int(min_points)
+
+
+def _cluster_keep_arguments(min_size, largest):
+    """cluster_keep's checks that need no device -> (min_size or None, largest): exactly one of the two rules"""
+    if not isinstance(largest, (bool, np.bool_)):
+        raise ValueError("cluster_keep: largest must be True or False, not %r" % (largest,))
+    if (min_size is None) == (not largest):
+        raise ValueError("cluster_keep: give min_size or largest=True, one of the two")
+    if min_size is not None and (isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer))
+                                 or not 1 <= int(min_size) <= 0x7fffffff):
+        raise ValueError("cluster_keep: min_size must be a positive integer, not %r" % (min_size,))
+    return None if min_size is None else int(min_size), bool(largest)
+
+
 ISS_DEFAULTS = {"salient_radius": None, "non_max_radius": None, "gamma_21": 0.975, "gamma_32": 0.975,
                 "min_neighbors": 5, "min_ratio": 1e-6}
 
@@ -318,6 +340,53 @@ class FragmentOverlap(object):
         N.check(N.lib().mvr_radius_count(*self._points(), *self._fragments(), radius, N.ptr(count), N.stream()),
                 "mvr_radius_count")
         return {"keep": count > nb_points, "count": count}
+
+    def cluster_dbscan(self, eps=None, min_points=10):
+        """Open3D's cluster_dbscan(eps, min_points) per fragment, restated (csrc/dbscan.hip mvr_cluster_dbscan; the
+        semantics are in include/mvreg.h): a point is core when at least min_points points of its fragment, itself
+        among them, lie closer than eps (None: fo.r; at most fo.r); a cluster is a connected component of the core
+        points, numbered per fragment from 0 by its smallest core row; any other point takes the lowest-numbered
+        cluster among its core neighbours, or -1 (noise).
+        -> {"labels": int32 [M], "sizes": int32 [M] (sizes[fo.off[b] + c]: the points of cluster c of fragment b, 0
+        beyond its clusters), "core": bool [M]} on the device and "n_clusters": numpy int64 [B]; cluster_keep turns
+        them into a mask for fo.select."""
+        eps, min_points = _dbscan_arguments(eps, min_points, self.r)
+        L = N.lib()
+        labels = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        sizes = torch.empty(self.M, dtype=torch.int32, device=self.device)
+        core = torch.empty(self.M, dtype=torch.uint8, device=self.device)
+        n_clusters = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        ws_b = L.mvr_dbscan_workspace_bytes(self.M)
+        ws = N.workspace(ws_b, self.device)
+        N.check(L.mvr_cluster_dbscan(*self._points(), *self._fragments(), eps, min_points, N.ptr(labels),
+                                     N.ptr(n_clusters), N.ptr(sizes), N.ptr(core), N.ptr(ws), ws_b, N.stream()),
+                "mvr_cluster_dbscan")
+        return {"labels": labels, "n_clusters": n_clusters.cpu().numpy().astype(np.int64), "sizes": sizes,
+                "core": core.bool()}
+
+    def cluster_keep(self, clusters, min_size=None, largest=False):
+        """The mask of a cluster filter from cluster_dbscan's dict -> bool [M] on the device, for fo.select: the
+        points of the clusters with at least min_size points, or with largest=True of each fragment's largest cluster
+        (on a tie the lowest number; Open3D users' "keep the largest cluster").  Noise is never kept.  Computed on the
+        device from labels and sizes."""
+        min_size, largest = _cluster_keep_arguments(min_size, largest)
+        labels, sizes = clusters["labels"], clusters["sizes"]
+        for what, x in (("labels", labels), ("sizes", sizes)):
+            if not torch.is_tensor(x) or tuple(x.shape) != (self.M,) or x.dtype != torch.int32 or \
+                    x.device != self.xyz.device:
+                raise ValueError("cluster_keep: clusters[%r] must be an int32 [%d] tensor on the device of fo.xyz"
+                                 % (what, self.M))
+        n_b = torch.from_numpy(np.diff(self.off)).to(self.device)
+        frag = torch.repeat_interleave(torch.arange(self.B, device=self.device), n_b, output_size=self.M)
+        first = self.off_dev[frag]                               # the first row of each row's fragment
+        labelled = labels >= 0
+        if not largest:
+            return labelled & (sizes[first + labels.clamp(min=0)] >= min_size)
+        number = torch.arange(self.M, device=self.device) - first     # row off[b] + c holds the size of cluster c
+        top = torch.zeros(self.B, dtype=torch.int32, device=self.device).scatter_reduce(0, frag, sizes, "amax")
+        best = torch.full((self.B,), self.M, dtype=torch.int64, device=self.device).scatter_reduce(
+            0, frag, torch.where(sizes == top[frag], number, torch.full_like(number, self.M)), "amin")
+        return labelled & (labels == best[frag])
 
     def iss_keypoints(self, salient_radius=None, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5,
                       min_ratio=1e-6):

@@ -12,6 +12,8 @@ refinement and the fused cloud, all on the GPU.  Writes into --out
 gate is an uncertain edge); the pairs it pruned are counted in the printed line.
 --denoise statistical:20:2.0 | radius:16[:R]: Open3D's statistical / radius outlier removal on each fragment's centroids
 before anything else uses them; the points removed per fragment are printed.
+--denoise cluster:MIN_POINTS:MIN_SIZE[:EPS]: Open3D's cluster_dbscan(EPS, MIN_POINTS) on each fragment's centroids (EPS
+defaults to 3 voxel sizes, its largest value); the clusters of fewer than MIN_SIZE points and the noise are removed.
 --keypoints iss[:SALIENT:NONMAX]: ISS keypoints (Open3D's compute_iss_keypoints; radii default to 3 and 2 voxel sizes)
 are detected on each fragment and the FPFH matching runs on them alone; the keypoints per fragment are printed.
 --icp_kernel huber|cauchy|gm|tukey|l2[:K]: the ICP stage weighs every correspondence by a robust kernel of scale K
@@ -57,18 +59,22 @@ def read_init(filename, n_fragments):
 
 
 def parse_denoise(text):
-    """'statistical:NB:RATIO' or 'radius:NB[:R]' -> register_scene's denoise dict (ValueError on anything else)"""
+    """'statistical:NB:RATIO', 'radius:NB[:R]' or 'cluster:MIN_POINTS:MIN_SIZE[:EPS]' -> register_scene's denoise dict
+    (ValueError on anything else)"""
     parts = text.split(":")
     try:
         if parts[0] == "statistical" and len(parts) == 3:
             d = {"method": "statistical", "nb_neighbors": int(parts[1]), "std_ratio": float(parts[2])}
         elif parts[0] == "radius" and len(parts) in (2, 3):
             d = {"method": "radius", "nb_points": int(parts[1]), "radius": float(parts[2]) if len(parts) == 3 else None}
+        elif parts[0] == "cluster" and len(parts) in (3, 4):
+            d = {"method": "cluster", "min_points": int(parts[1]), "min_size": int(parts[2]),
+                 "eps": float(parts[3]) if len(parts) == 4 else None}
         else:
             raise ValueError("neither form")
     except ValueError:
-        raise ValueError("--denoise must be statistical:NB_NEIGHBORS:STD_RATIO or radius:NB_POINTS[:RADIUS], not %r"
-                         % (text,))
+        raise ValueError("--denoise must be statistical:NB_NEIGHBORS:STD_RATIO, radius:NB_POINTS[:RADIUS] or "
+                         "cluster:MIN_POINTS:MIN_SIZE[:EPS], not %r" % (text,))
     return d
 
 
@@ -139,7 +145,9 @@ def parser():
     ap.add_argument("--denoise", default=None, metavar="SPEC",
                     help="remove outliers from the centroids before registration: statistical:20:2.0 (Open3D's "
                          "remove_statistical_outlier(nb_neighbors, std_ratio)) or radius:16[:R] "
-                         "(remove_radius_outlier(nb_points, radius), R at most 3 voxel_size, its default)")
+                         "(remove_radius_outlier(nb_points, radius), R at most 3 voxel_size, its default), or keep "
+                         "the DBSCAN clusters of at least MIN_SIZE points: cluster:10:100[:EPS] "
+                         "(cluster_dbscan(eps, min_points), EPS at most 3 voxel_size, its default)")
     ap.add_argument("--keypoints", default=None, metavar="SPEC",
                     help="match the FPFH descriptors of ISS keypoints only: iss, or iss:SALIENT:NONMAX (Open3D's "
                          "compute_iss_keypoints radii, each at most 3 voxel_size; defaults 3 and 2 voxel_size); not "

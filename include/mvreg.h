@@ -397,7 +397,7 @@ int mvr_voxel_centroids_colored(const float* xyz, const int64_t* frag_off, int B
  * size r) + a hash of the occupied cells.  `index` holds mvr_radius_index_bytes(M) bytes and stays valid
  * for mvr_radius_overlap_count, mvr_icp_refine, mvr_estimate_normals, mvr_icp_refine_plane,
  * mvr_icp_refine_generalized, mvr_compute_fpfh, mvr_knn_self, mvr_radius_count, mvr_iss_saliency, mvr_radius_nms,
- * mvr_color_gradient and mvr_icp_refine_colored calls on the same points.
+ * mvr_color_gradient, mvr_icp_refine_colored and mvr_cluster_dbscan calls on the same points.
  * B < 32768.
  * Cell keys: the cell coordinate floor(x / r) + 2^15 is kept modulo 2^16 per axis, so coordinates are NOT limited:
  * cells 65536 r apart along an axis (3,276.8 m at r = 0.05) share a key.  That aliasing is harmless: the aliased
@@ -754,6 +754,40 @@ int mvr_statistical_outlier(const double* dist2, const int64_t* off, int B, int6
                             uint8_t* keep, double* mean_dist, double* thr, mvr_stream_t stream);
 int mvr_radius_count(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
                      double r_index, double radius, int32_t* count, mvr_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * DBSCAN clustering of every fragment's own points, on a radius index (csrc/dbscan.hip): what
+ * Open3D's cluster_dbscan(eps, min_points) returns when it is called per fragment, restated from the definition;
+ * Open3D parity is unpinned.  tests/dbscan_oracle.py restates Open3D's sequential loop in numpy.
+ *   index, xyz [M,3], off [B+1], r_index: the arguments of the mvr_radius_index_build call that made `index`.
+ *   Neighbourhood: N(i) = the rows t of i's fragment with sqrt(ex*ex + ey*ey + ez*ez) < eps, e = x_t - x_i: the
+ *   expression, the strictness and the inclusion of i itself (and of its duplicates) of mvr_radius_count (one walk,
+ *   csrc/rindex.hpp), so the relation is symmetric bit for bit.  Open3D and sklearn take d <= eps: the results differ
+ *   only where a distance equals eps exactly.
+ *   Core: row i is core iff |N(i)| >= min_points.
+ *   Clusters: the connected components of the graph on the core rows with an edge i - t iff t is in N(i).  A
+ *   fragment's clusters are numbered 0 .. n_b - 1 by ascending smallest core row.
+ *   Border: a row that is not core with at least one core row in N(i) takes the lowest-numbered cluster among its
+ *   core neighbours' clusters.  Noise: every other row that is not core, label -1.
+ *   That is what the sequential loop (Open3D's, sklearn's) returns: it grows the clusters one after another in
+ *   seed order, a cluster is first reached at its smallest core row, and a border point keeps the first cluster
+ *   that reaches it, the lowest-numbered one.
+ *   Outputs: labels [M] (the cluster's number within its fragment, or -1); n_clusters [B] (0 for an empty
+ *   fragment); sizes [M] or NULL: sizes[off[b] + c] = the points labelled c in fragment b, 0 for c >= n_clusters[b],
+ *   all M entries written; core [M] or NULL: 1 / 0.  Nothing is written behind these extents.
+ *   The outputs are a pure function of the fragment's points and their row order: bit-identical whatever other
+ *   fragments are in the batch, whatever the launch geometry, and from run to run (the components are united by
+ *   lock-free hooking of the larger root under the smaller, whose result, the smallest core row as the root, does not
+ *   depend on the interleaving; no thread waits for another).  No host synchronisation.
+ *   MVR_EINVAL, scalars first: negative M or M >= 2^31; B <= 0 or B >= 32768; r_index <= 0; eps outside
+ *   (0, r_index] (a NaN is outside); min_points < 1.  M == 0 then returns MVR_OK with nothing written.  With M > 0: a
+ *   NULL index, xyz, off, labels, n_clusters or workspace, index_bytes < mvr_radius_index_bytes(M), or
+ *   workspace_bytes < mvr_dbscan_workspace_bytes(M).
+ * ---------------------------------------------------------------------- */
+size_t mvr_dbscan_workspace_bytes(int64_t M);
+int mvr_cluster_dbscan(const void* index, size_t index_bytes, const double* xyz, const int64_t* off, int B, int64_t M,
+                       double r_index, double eps, int min_points, int32_t* labels, int32_t* n_clusters,
+                       int32_t* sizes, uint8_t* core, void* workspace, size_t workspace_bytes, mvr_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * ISS keypoints (Intrinsic Shape Signatures, Zhong 2009) of every fragment's own points, on a radius index
